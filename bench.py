@@ -24,6 +24,12 @@ am_key_partition(key, 64) % N == r), so value = N * ops per GPU / step time.
 
 Launch: python bench.py [--gpus 1 --steps K --warmup W --config c3 --base fresh]; for N > 1
 under torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_ADDR from the env).
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step).
+--full adds everything that takes runs of its own: HIP-event times of each step, the read call
+alone (kernel_ms) and the roofline figures built on it, the secondary lines (cached C3, the
+indexed reads, C4, C5, C2) and the CPU baseline.  --dump-outputs DIR writes the result columns of
+the last timed step (a fixed sample of the reads) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -468,9 +474,67 @@ class Step:
         self.store.close()
 
 
-def measure(st: Step, base: str, steps: int, warmup: int, barrier, pg, timed_wall: bool = True):
-    """Time `steps` steps of one config (after `warmup`), then the read call alone.  Returns the
-    measured figures (max over ranks of the wall time when pg is given)."""
+DUMP_BUDGET = 48 << 20     # bytes of .npy data --dump-outputs writes at most (float64 columns)
+DUMP_SEED = 0x5eed         # the read sample is the same from run to run and from build to build
+
+
+def dump_outputs(st: Step, out_dir: str):
+    """Write what the last step returned to its caller (the am_read_result columns of st.reads) as
+    out_dir/<name>.npy, float64, for a fixed seeded sample of the reads (`read_index`, ascending;
+    every read when they fit in DUMP_BUDGET).  64-bit columns are split into exact 32-bit halves
+    (<name>_lo, <name>_hi); set pairs / bounded-counter entries keep the order the library
+    returned them in, one row per read as wide as the batch's largest value capacity, zero past the
+    read's set_len."""
+    r = st.reads
+    n, nd = r.n, r.n_dc
+    if r.dev.type == "cuda":
+        torch.cuda.synchronize()
+    st.mat.sync()
+    cap = 0
+    if r.set_len is not None:
+        cap = int((r.set_off[1:] - r.set_off[:-1]).max().item())
+    per_read = 8 * (1 + 8 + 2 + 2 * nd + 4 + 4 * cap)
+    k = int(min(n, DUMP_BUDGET // per_read))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    d_idx = torch.from_numpy(idx.astype(np.int64)).to(r.dev)
+    cols = {"read_index": idx.astype(np.float64)}
+
+    def put(name, t):
+        cols[name] = t.cpu().numpy().astype(np.float64)
+
+    def put64(name, t):
+        u = t.cpu().numpy().view(np.uint64)
+        cols[name + "_lo"] = (u & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        cols[name + "_hi"] = (u >> np.uint64(32)).astype(np.float64)
+
+    for name in ("status", "last_ct_pres", "last_ct_ignore", "is_new_ss", "count", "flags", "vflag"):
+        put(name, getattr(r, name)[d_idx])
+    put64("new_last_op", r.new_last_op[d_idx])
+    put64("last_ct", r.last_ct[:, d_idx])
+    put64("v0", r.v0[d_idx])
+    put64("v1", r.v1[d_idx])
+    if r.set_len is not None:
+        sl = r.set_len[d_idx].to(torch.int64)
+        put("set_len", sl)
+        j = torch.arange(cap, dtype=torch.int64, device=r.dev)
+        valid = j[None, :] < sl[:, None]
+        pos = torch.where(valid, r.set_off[d_idx][:, None] + j[None, :], 0)
+        put64("set_a", torch.where(valid, r.set_a[pos], 0))
+        put64("set_b", torch.where(valid, r.set_b[pos], 0))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
+def measure(st: Step, base: str, steps: int, warmup: int, barrier, pg, timed_wall: bool = True, full: bool = True,
+            after_timed=None):
+    """Time `steps` steps of one config (after `warmup`), then (full) each step under HIP events
+    and the read call alone.  after_timed(), if given, runs right after the timed steps, while
+    st.reads still holds the last timed step's results.  Returns the measured figures (max over
+    ranks of the wall time when pg is given)."""
     mat = st.mat
 
     def stat(reset, which):
@@ -518,6 +582,10 @@ def measure(st: Step, base: str, steps: int, warmup: int, barrier, pg, timed_wal
     assert (stt == 0).all(), f"materialize returned errors: {np.unique(stt, return_counts=True)}"
     gst_vc = st.reads.read_vc.cpu().numpy().view(np.uint64)
     assert [int(x) for x in gst_vc] == [int(st.clock[d]) for d in range(st.cfg["n_dc"])], "GST mismatch"
+    if after_timed is not None:
+        after_timed()
+    if not full:
+        return {"dt": dt, "steps": steps, "packed": bool(st.dlog.pk_vc)}
 
     kern_iters = max(5, steps)
     zs = np.zeros(3)  # per launch: ops skipped by the zone index, records skipped, summary words read
@@ -590,6 +658,13 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary lines (c3: cached c3, the indexed reads, c4, c5 and c2; single GPU "
                          "only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: HIP-event step times, the read call alone and "
+                         "the roofline built on it, the secondary lines and the CPU baseline (see --no-secondary, "
+                         "--no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result columns (a fixed sample of the "
+                         "reads) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -642,8 +717,9 @@ def main():
     st = Step(mat, comm, cfg, rank, world, level)
     if args.base == "cached":
         st.populate()
-    m = measure(st, args.base, args.steps, args.warmup, barrier, pg)
-    if level == abi.AM_INDEX_NONE:
+    dump = (lambda: dump_outputs(st, args.dump_outputs)) if args.dump_outputs and rank == 0 else None
+    m = measure(st, args.base, args.steps, args.warmup, barrier, pg, full=args.full, after_timed=dump)
+    if args.full and level == abi.AM_INDEX_NONE:
         assert m["skipped"] == 0 and m["rskip"] == 0, "the op-streaming headline skipped ops"
 
     n_dc, n_keys, type_ = cfg["n_dc"], cfg["n_keys"], cfg["type"]
@@ -651,7 +727,7 @@ def main():
     value = total_ops / m["dt"]
     workload = f"{args.config}: {cfg['desc']}"
     single = type_ in (abi.AM_PN, abi.AM_LWW)
-    dt, kern_ms, achieved, logical = m["dt"], m["kern_ms"], m["achieved"], m["logical"]
+    dt = m["dt"]
     out = {
         "metric": "CRDT ops materialized/sec (whole node) + % HBM peak",
         "value": value,
@@ -660,8 +736,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3,
-        "step_ms_hip_events": {"median": float(np.median(m["step_ev"])), "mean": float(np.mean(m["step_ev"])),
-                               "min": float(np.min(m["step_ev"])), "n": len(m["step_ev"])},
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -676,37 +750,42 @@ def main():
                            "timing of each step",
                    "base": args.base, "zone_index": INDEX_NAMES[level],
                    "store_build_s": st.build_s, "src_sha16": src_sha16()},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS,
-                     "model": "layout bytes (DESIGN.md 4): what the kernels stream of this build's HBM layout -- "
-                              "commit vectors (packed: 4*D per op; lag view, for the reads of the tiers that stream it "
-                              "(bench.lag_keys): 4 + 2*D per op and 4*D per read), "
-                              "payload, 4 B per token-group record or 8 B per group-mask op, per-read metadata and "
-                              "outputs; every op streamed (no zone index)"
-                              if level == abi.AM_INDEX_NONE else
-                              "layout bytes (DESIGN.md 4) minus the commit vectors / records the zone index stood in for",
-                     "traffic": load_traffic(args.config if args.base == "fresh" else args.config + "_cached", workload,
-                                             INDEX_NAMES[level]),
-                     "kernel": ("am_snapcache_read (select + materialize tiers + store)" if args.base == "cached"
-                                else "k_stream" if single else
-                                "am_materialize (all tiers: k_stream, k_rows, k_grp_*, k_sets, k_big_*)"),
-                     "kernel_ms": kern_ms,
-                     "kernel_ms_median": m["kern_ms_median"],
-                     "logical": {"model": "SURVEY.md 8(d) B_op / B_key (the reference's per-op record: "
-                                          "8*D + 17 + P_type per op)", "bytes_per_launch": logical,
-                                 "bytes_per_s": logical / (kern_ms * 1e-3),
-                                 "frac_of_peak": logical / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                     "alg_bytes_per_launch": m["alg_bytes"],
-                     "ops_skipped_per_launch": m["skipped"], "records_skipped_per_launch": m["rskip"],
-                     "gsum_words_per_launch": m["gsw"],
-                     "layout": ("lag view (u32 commit time + u16 lag per DC, relative to per-key bases)"
-                                if lag_split(cfg, st.dlog, level) else
-                                "packed (u32 commit vectors relative to a per-key time base)")
-                               + "; set effects as u32 token-group records" if m["packed"] else "full"},
         "cpu_baseline": None,
     }
+    if args.full:
+        kern_ms, achieved, logical = m["kern_ms"], m["achieved"], m["logical"]
+        out["step_ms_hip_events"] = {"median": float(np.median(m["step_ev"])), "mean": float(np.mean(m["step_ev"])),
+                                     "min": float(np.min(m["step_ev"])), "n": len(m["step_ev"])}
+        roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                "model": "layout bytes (DESIGN.md 4): what the kernels stream of this build's HBM layout -- "
+                         "commit vectors (packed: 4*D per op; lag view, for the reads of the tiers that stream it "
+                         "(bench.lag_keys): 4 + 2*D per op and 4*D per read), "
+                         "payload, 4 B per token-group record or 8 B per group-mask op, per-read metadata and "
+                         "outputs; every op streamed (no zone index)"
+                         if level == abi.AM_INDEX_NONE else
+                         "layout bytes (DESIGN.md 4) minus the commit vectors / records the zone index stood in for",
+                "traffic": load_traffic(args.config if args.base == "fresh" else args.config + "_cached", workload,
+                                        INDEX_NAMES[level]),
+                "kernel": ("am_snapcache_read (select + materialize tiers + store)" if args.base == "cached"
+                           else "k_stream" if single else
+                           "am_materialize (all tiers: k_stream, k_rows, k_grp_*, k_sets, k_big_*)"),
+                "kernel_ms": kern_ms,
+                "kernel_ms_median": m["kern_ms_median"],
+                "logical": {"model": "SURVEY.md 8(d) B_op / B_key (the reference's per-op record: "
+                                     "8*D + 17 + P_type per op)", "bytes_per_launch": logical,
+                            "bytes_per_s": logical / (kern_ms * 1e-3),
+                            "frac_of_peak": logical / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                "alg_bytes_per_launch": m["alg_bytes"],
+                "ops_skipped_per_launch": m["skipped"], "records_skipped_per_launch": m["rskip"],
+                "gsum_words_per_launch": m["gsw"],
+                "layout": ("lag view (u32 commit time + u16 lag per DC, relative to per-key bases)"
+                           if lag_split(cfg, st.dlog, level) else
+                           "packed (u32 commit vectors relative to a per-key time base)")
+                          + "; set effects as u32 token-group records" if m["packed"] else "full"}
+        out["roofline"] = roof
 
-    secondary = world == 1 and args.config == "c3" and args.base == "fresh" and not args.no_secondary
+    secondary = args.full and world == 1 and args.config == "c3" and args.base == "fresh" and not args.no_secondary
     if secondary:
         sec = {}
         ksteps = max(5, min(args.steps, 10))
@@ -737,7 +816,7 @@ def main():
             sec[c]["traffic"] = load_traffic(c, f"{c}: " + CONFIGS[c]["desc"], "none")
             sx.close()
         out["secondary"] = sec
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         p = st.p if st is not None else synth_params(cfg, rank, world)
         out["cpu_baseline"] = cpu_baseline(cfg, p, budget_s=args.cpu_budget, cached=args.base == "cached")
     if rank == 0:

@@ -10,7 +10,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for e in $ENVS; do
     tag=$(echo "$e" | tr ',=' '__')
     if [ "$e" = "-" ]; then envs=(); else IFS=',' read -ra envs <<< "$e"; fi
-    timeout -k 10 300 env "${envs[@]}" python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline \
+    timeout -k 10 300 env "${envs[@]}" python bench.py --full --config $CFG --steps 20 --warmup 3 --no-cpu-baseline \
       > $OUT/abe_${CFG}_${tag}_$r.json 2> $OUT/abe_${CFG}_${tag}_$r.err
     rc=$?; echo "[abe $CFG $e $r] rc=$rc $(python -c "import json;d=json.load(open('$OUT/abe_${CFG}_${tag}_$r.json'));print(round(d['ms_per_step'],3), round(d['roofline']['kernel_ms'],3))" 2>/dev/null)" | tee -a $OUT/steps.log
     if [ $rc -ne 0 ]; then exit $rc; fi

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Markdown rows for BASELINE.md / DESIGN.md from bench.py JSON lines:
+"""Markdown rows for BASELINE.md / DESIGN.md from `bench.py --full` JSON lines:
    python scripts/baseline_table.py profiles/r04/final/bench_c3.json ...  (one JSON line per file)"""
 import json
 import sys

@@ -16,7 +16,7 @@ for v in ${VARS:-old quad}; do
       F) ctr="FETCH_SIZE" ;;
       W) ctr="WRITE_SIZE" ;;
     esac
-    AM_LIB=$PWD/scripts/ab/lib_$v.so timeout -s KILL 120 rocprofv3 --pmc $ctr -d $OUT/pm_${CFG}_${v}_$p -o pmc --output-format csv -- python bench.py --config $CFG --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pm_${CFG}_${v}_$p.log 2>&1
+    AM_LIB=$PWD/scripts/ab/lib_$v.so timeout -s KILL 120 rocprofv3 --pmc $ctr -d $OUT/pm_${CFG}_${v}_$p -o pmc --output-format csv -- python bench.py --full --config $CFG --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pm_${CFG}_${v}_$p.log 2>&1
     rc=$?; echo "[pmc $CFG $v $p] rc=$rc" | tee -a $OUT/steps.log
     if [ $rc -ne 0 ]; then exit $rc; fi
   done

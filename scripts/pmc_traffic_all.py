@@ -1,6 +1,6 @@
 """HBM traffic per materialize launch summed over EVERY materialize kernel (the lane, row,
 stream, group, LDS-sort and big-read tiers and the planner) from rocprofv3 --pmc FETCH_SIZE
-and WRITE_SIZE passes (separate runs) of `bench.py --config CFG`; one launch = one k_lane
+and WRITE_SIZE passes (separate runs) of `bench.py --full --config CFG`; one launch = one k_lane
 (or k_grp_wave) dispatch.  Writes profiles/pmc_traffic.json[CFG].
 Usage: pmc_traffic_all.py FETCH_DIR WRITE_DIR CFG WORKLOAD LAUNCH_KERNEL [OUT [ZONE_INDEX]]
 (ZONE_INDEX: the store's zone index level name, bench.py INDEX_NAMES; default "none")"""
