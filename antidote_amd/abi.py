@@ -93,7 +93,7 @@ class am_synth_params(ctypes.Structure):
         ("seed", c_uint64), ("n_keys", c_uint64), ("ops_per_key", c_uint32), ("n_dc", c_uint32),
         ("type", c_uint32), ("key_base", c_uint32), ("max_lag", c_uint32), ("zipf_milli", c_uint32),
         ("total_ops", c_uint64), ("hot_cap", c_uint32), ("universe", c_uint32), ("part_mask", c_uint64),
-        ("esc_ppm", c_uint32), ("_pad2", c_uint32),
+        ("esc_ppm", c_uint32), ("gst_ppm", c_uint32),
     ]
 
 
@@ -103,6 +103,11 @@ AM_STAT_RECS_SKIPPED = 1
 AM_STAT_GSUM_WORDS = 2
 AM_ZONE_OPS = 256
 AM_INDEX_NONE, AM_INDEX_ZONES, AM_INDEX_EXACT, AM_INDEX_SUMMARIES = 0, 1, 2, 3
+# am_store_view_stats counters, in order (AM_VIEW_STAT_*)
+VIEW_STATS = ("ops", "pk_esc_ops", "lag_only_esc_ops", "routed_keys", "routed_ops")
+AM_VIEW_STAT_N = len(VIEW_STATS)
+AM_PK_ESC = 0xFFFFFFFF
+AM_LAG_ROUTED = -(1 << 31)  # key_lag[k][0] of a packed-routed key
 AM_ERR_COLD_PATH = 5
 AM_SNAPSHOT_THRESHOLD = 10
 AM_SNAPCACHE_ABSENT = 0xFFFFFFFF
@@ -130,6 +135,7 @@ SIGNATURES = [
     ("am_store_log", c_int, [c_void_p, POINTER(am_op_log)]),
     ("am_store_destroy", c_int, [c_void_p]),
     ("am_store_index", c_int, [c_void_p, c_void_p, c_int]),
+    ("am_store_view_stats", c_int, [c_void_p, c_void_p, POINTER(c_uint64)]),
     ("am_materialize", c_int, [c_void_p, POINTER(am_op_log), POINTER(am_read_batch), POINTER(am_read_result)]),
     ("am_materialize_host", c_int, [c_void_p, c_void_p, POINTER(am_read_batch), POINTER(am_read_result)]),
     ("am_gst_local_min", c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -221,7 +227,7 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
-        if L.am_abi_version() != 12:
+        if L.am_abi_version() != 13:
             raise AmError("ABI version mismatch")
         _lib = L
     return _lib

@@ -202,9 +202,15 @@ __global__ void __launch_bounds__(256) k_writeback(am_op_log L, am_op_log S, con
       }
     }
     for (uint64_t q = d0 + n + lane; L.gmask && q < cap_end; q += WAVE_SZ) const_cast<uint64_t *>(L.gmask)[q] = 0;
+    // the slots a shrunk key frees stay escaped, as every free slot of the lag view is
+    for (uint64_t q = d0 + n + lane; L.lag_ct && q < cap_end; q += WAVE_SZ)
+      const_cast<uint32_t *>(L.lag_ct)[q] = AM_PK_ESC;
+    // the key's lag bases with its routing mark (S's decision over the merged key; without S's
+    // lag view every op above was written escaped: routed, when the key has ops)
     if (L.key_lag)
       for (uint32_t d = lane; d < L.n_dc; d += WAVE_SZ)
-        const_cast<int32_t *>(L.key_lag)[k * L.n_dc + d] = (S.key_lag && S.lag_ct) ? S.key_lag[i * S.n_dc + d] : 0;
+        const_cast<int32_t *>(L.key_lag)[k * L.n_dc + d] =
+            (S.key_lag && S.lag_ct && S.lag) ? S.key_lag[i * S.n_dc + d] : (d == 0 && n ? AM_LAG_ROUTED : 0);
     if (L.zone_vc)  // the blocks inside the key: maxima, marks and summaries recomputed
       zone_rewrite(L, S, i, d0, n, cap_end, L.rec_key_off ? L.rec_key_off[k] : 0, zlevel, lane,
                    zbits[threadIdx.x / WAVE_SZ]);

@@ -76,7 +76,7 @@ __device__ __forceinline__ uint32_t row_max_u32(uint32_t v) {
 #endif
 template <int DMAX, bool LAG>
 __global__ void __launch_bounds__(BLOCK, AM_BCR_WAVES) k_bc_rows(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
-                                                   am_retry next) {
+                                                   am_retry next, am_retry routed) {
   __shared__ BcrSmem smem[BLOCK / WAVE];
   BcrSmem &sm = smem[threadIdx.x / WAVE];
   const uint32_t lane = threadIdx.x & (WAVE - 1), row = lane / RG, sl = lane % RG;
@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(BLOCK, AM_BCR_WAVES) k_bc_rows(am_op_log L, am
   for (uint64_t rb = gw * WAVE; rb < nsel; rb += W * WAVE) {
     // ---- lane i: read rb + i -> status | hand-off | taken (published for its row) ----
     const uint64_t i = rb + lane;
-    bool take = false, hand = false;
+    bool take = false, hand = false, route = false;
     uint64_t r = 0;
     if (i < nsel) {
       r = S.idx ? (uint64_t)S.idx[sel0 + i] : i;
@@ -122,6 +122,8 @@ __global__ void __launch_bounds__(BLOCK, AM_BCR_WAVES) k_bc_rows(am_op_log L, am
         R.status[r] = st, R.flags[r] = 0;
       } else if (off1 - off0 > BCR_OPS) {
         hand = true;
+      } else if (LAG && routed.list && L.key_lag[key * nd] == AM_LAG_ROUTED) {
+        route = true;  // a packed-routed key: the packed instantiation's (launch_d)
       } else {
         take = true;
         BcrIn &w = sm.in[lane];
@@ -142,6 +144,7 @@ __global__ void __launch_bounds__(BLOCK, AM_BCR_WAVES) k_bc_rows(am_op_log L, am
       base = uniform_u32(base);
       if (hand) next.list[base + (uint32_t)__popcll(hm & lt)] = (uint32_t)r;
     }
+    if (LAG) retry_append(routed, route, (uint32_t)r, lane);
     const uint64_t tm = __ballot(take);
     wave_sync();
 
@@ -265,10 +268,14 @@ __global__ void __launch_bounds__(BLOCK, AM_BCR_WAVES) k_bc_rows(am_op_log L, am
           const uint32_t t = (uint32_t)__builtin_ctz(tb);
           const uint64_t p = a0 + (uint64_t)RG * t + owner;
           const uint32_t q = (uint32_t)(p - in.off0);
-          const uint64_t *w = esc_row(L, stride, p);  // its escape row, or the columns
+          // a lag-only escape (the packed view holds the op): lane d's packed entry, K + entry;
+          // else its escape row, or the columns
+          const bool pkd = LAG && L.pk_vc[p] != AM_PK_ESC;
+          const uint64_t *w = pkd ? nullptr : esc_row(L, stride, p);
           const uint32_t meta = w ? (uint32_t)w[1] : L.op_meta[p], dc = meta & 31u;
           uint64_t xd = 0;
-          if (sl < nd) xd = sl == dc ? (w ? w[0] : L.commit_time[p]) : (w ? w[2 + sl] : L.snap_vc[(uint64_t)sl * stride + p]);
+          if (sl < nd && pkd) xd = in.K + L.pk_vc[(uint64_t)sl * stride + p];
+          else if (sl < nd) xd = sl == dc ? (w ? w[0] : L.commit_time[p]) : (w ? w[2 + sl] : L.snap_vc[(uint64_t)sl * stride + p]);
           const bool failx = sl < nd && (!((u.spres >> sl) & 1u) || xd > vS);
           const bool included = row_or_u32(failx ? 1u : 0u) == 0;
           if (sl == 0) fl |= miss;
@@ -382,7 +389,17 @@ int launch_dl(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_read_r
   uint64_t blocks = (batches + BLOCK / WAVE - 1) / (BLOCK / WAVE), cap = (uint64_t)ctx->n_cu * occ;
   if (blocks > cap) blocks = cap;
   if (blocks == 0) return AM_OK;
-  hipLaunchKernelGGL((k_bc_rows<D, LAG>), dim3((unsigned)blocks), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S, next);
+  // the lag instantiation leaves the reads of packed-routed keys in a list; the packed
+  // instantiation takes exactly those (an empty list: its blocks return at once)
+  am_retry routed;
+  am_sel rsel;
+  if (LAG)
+    if (int rc = am_route_list(ctx, B->n_reads, &routed, &rsel)) return rc;
+  hipLaunchKernelGGL((k_bc_rows<D, LAG>), dim3((unsigned)blocks), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S, next,
+                     routed);
+  if (LAG)
+    hipLaunchKernelGGL((k_bc_rows<D, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, rsel,
+                       next, am_retry{});
   AM_HIP(hipGetLastError());
   return AM_OK;
 }

@@ -198,7 +198,7 @@ __global__ void __launch_bounds__(BLOCK) k_bc_wave(am_op_log L, am_read_batch B,
           if (L.pk_vc[p] != AM_PK_ESC) continue;
           uint64_t sv[DMAX], ct;
           uint32_t meta;
-          esc_load<DMAX>(L, nd, stride, p, sv, ct, meta);
+          esc_load<DMAX>(L, nd, stride, p, NONE, sv, ct, meta);  // (the loop streamed pk_vc)
           if (eval_op<DMAX, false>(u, meta, ct, sv, u.allmask, false, p, a))
             apply(meta, (int64_t)L.p0[p], L.p1[p]);
         }
@@ -214,9 +214,16 @@ __global__ void __launch_bounds__(BLOCK) k_bc_wave(am_op_log L, am_read_batch B,
         const uint32_t *escv = lr.on ? L.lag_ct : L.pk_vc;  // the view the loop streamed
         for (uint64_t p = off0 + lane; p < off1; p += WAVE) {
           if (escv[p] != AM_PK_ESC) continue;
-          const uint64_t *w = esc_row(L, stride, p);  // its escape row, or the columns
+          // a lag-only escape (the packed view holds the op): its packed entries, K + entry;
+          // else its escape row, or the columns
+          const bool pkd = L.pk_vc[p] != AM_PK_ESC;
+          const uint64_t *w = pkd ? nullptr : esc_row(L, stride, p);
           const uint32_t meta = w ? (uint32_t)w[1] : L.op_meta[p], dc = meta & 31u;
-          const uint64_t ct = w ? w[0] : L.commit_time[p];
+          auto xd = [&](uint32_t d) -> uint64_t {
+            if (pkd) return pk.K + L.pk_vc[(uint64_t)d * stride + p];
+            if (d == dc) return w ? w[0] : L.commit_time[p];
+            return w ? w[2 + d] : L.snap_vc[(uint64_t)d * stride + p];
+          };
           bool incl = true;
           for (uint32_t d = 0; d < nd; ++d) {
             if (!((u.spres >> d) & 1u)) {  // logger:error("Could not find DC in SS"); excluded
@@ -224,17 +231,13 @@ __global__ void __launch_bounds__(BLOCK) k_bc_wave(am_op_log L, am_read_batch B,
               a.flags |= AM_FLAG_MISSING_DC_LOGGED;
               continue;
             }
-            const uint64_t x = d == dc ? ct : (w ? w[2 + d] : L.snap_vc[(uint64_t)d * stride + p]);
-            incl &= x <= lane_u64(vS, d);
+            incl &= xd(d) <= lane_u64(vS, d);
           }
           if (!incl) {
             a.min_excl = p < a.min_excl ? p : a.min_excl;
             continue;
           }
-          for (uint32_t d = 0; d < nd; ++d) {
-            const uint64_t x = d == dc ? ct : (w ? w[2 + d] : L.snap_vc[(uint64_t)d * stride + p]);
-            atomicMax((unsigned long long *)&s.emx[d], (unsigned long long)x);
-          }
+          for (uint32_t d = 0; d < nd; ++d) atomicMax((unsigned long long *)&s.emx[d], (unsigned long long)xd(d));
           a.pres |= u.allmask;
           a.count += 1;
           if (meta & AM_META_BAD) a.flags |= FLAG_BAD;

@@ -274,16 +274,17 @@ __device__ __forceinline__ uint32_t eval_tile(const am_op_log &L, uint32_t nd, c
 }
 
 // the escaped ops of ops [off0, off1) handled by this lane (p = off0 + lane0, step nl), from
-// the full columns; included ones are OR-ed into the LDS bitmap (bit = p - t0)
+// their packed entries (a lag-only escape; K: the key's time base) or the full columns
+// (esc_load); included ones are OR-ed into the LDS bitmap (bit = p - t0)
 template <int DMAX, bool GENERAL>
 __device__ __forceinline__ void esc_pass(const am_op_log &L, uint32_t nd, const ReadU<DMAX> &u, uint64_t off0,
                                       uint64_t off1, uint64_t t0, uint64_t stride, uint32_t lane0, uint32_t nl,
-                                      uint32_t *incl, Acc<DMAX> &a, const uint32_t *escv) {
+                                      uint32_t *incl, Acc<DMAX> &a, const uint32_t *escv, uint64_t K) {
   for (uint64_t p = off0 + lane0; p < off1; p += nl) {
     if (escv[p] != AM_PK_ESC) continue;
     uint64_t sv[DMAX], ct;
     uint32_t meta;
-    esc_load<DMAX>(L, nd, stride, p, sv, ct, meta);
+    esc_load<DMAX>(L, nd, stride, p, K, sv, ct, meta);
     const uint32_t sp = (GENERAL && L.snap_pres) ? L.snap_pres[p] : u.allmask;
     const bool txm = GENERAL && u.has_txid && L.op_txid[p] == u.txid;
     if (eval_op<DMAX, GENERAL>(u, meta, ct, sv, sp, txm, p, a) && !(meta & AM_META_BAD))
@@ -295,12 +296,13 @@ __device__ __forceinline__ void esc_pass(const am_op_log &L, uint32_t nd, const 
 // view the read streamed (pk_vc, or the lag view's lag_ct), whose AM_PK_ESC marks the escapes
 template <int DMAX>
 __device__ void esc_pass_g(const am_op_log &L, uint32_t nd, const ReadU<DMAX> &u, uint64_t off0, uint64_t off1,
-                           uint64_t stride, uint32_t lane, uint32_t *gbm, Acc<DMAX> &a, const uint32_t *escv) {
+                           uint64_t stride, uint32_t lane, uint32_t *gbm, Acc<DMAX> &a, const uint32_t *escv,
+                           uint64_t K) {
   for (uint64_t p = off0 + lane; p < off1; p += WAVE) {
     if (escv[p] != AM_PK_ESC) continue;
     uint64_t sv[DMAX], ct;
     uint32_t meta;
-    esc_load<DMAX>(L, nd, stride, p, sv, ct, meta);
+    esc_load<DMAX>(L, nd, stride, p, K, sv, ct, meta);
     if (eval_op<DMAX, false>(u, meta, ct, sv, u.allmask, false, p, a) && !(meta & AM_META_BAD))
       atomicOr(&gbm[p >> 5], 1u << (p & 31));
   }
@@ -468,7 +470,7 @@ __global__ void __launch_bounds__(WBLOCK, 4) k_grp_wg(am_op_log L, am_read_batch
     const bool full = !PACKED || __syncthreads_or(esc);
     if (PACKED && full)  // rare: ops outside the packed view, from the full columns
       esc_pass<DMAX, GENERAL>(L, nd, u, m.off0, m.off1, t0, stride, tid, WBLOCK, s.incl, a,
-                              lr.on ? L.lag_ct : L.pk_vc);
+                              lr.on ? L.lag_ct : L.pk_vc, lr.on ? pk.K : NONE);
     {  // wave partials of the scalar outputs (VGPR reductions: the scalar file is full)
       uint32_t cnt, fl, pr;
       uint64_t mn, mxl;
@@ -1075,7 +1077,8 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_op_log L, 
       wave_sync();
       const bool full = !BM && (!PACKED || __ballot(esc));
       if (PACKED && full) {  // rare: ops outside the packed view, from the full columns
-        esc_pass<DMAX, GENERAL>(L, nd, u, off0, off1, t0, stride, lane, WAVE, s.incl, a, lr.on ? L.lag_ct : L.pk_vc);
+        esc_pass<DMAX, GENERAL>(L, nd, u, off0, off1, t0, stride, lane, WAVE, s.incl, a, lr.on ? L.lag_ct : L.pk_vc,
+                                lr.on ? pk.K : NONE);
         wave_sync();
       }
 
@@ -1302,7 +1305,8 @@ __device__ __forceinline__ uint32_t incl_tile_lag(const uint32_t (&c)[4], const 
 #endif
 template <int DMAX, int TYPE, bool EXACT, bool LAG>
 __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
-                                                       am_retry next, uint32_t short_opl, uint32_t *ibm) {
+                                                       am_retry next, am_retry routed, uint32_t short_opl,
+                                                       uint32_t *ibm) {
   constexpr int OPL = 4;
   constexpr uint64_t TILE = (uint64_t)WAVE * OPL;
   constexpr uint32_t LPW = 32 / OPL;
@@ -1324,7 +1328,7 @@ __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, 
   for (uint64_t b0 = gw * IWB; b0 < nsel; b0 += (uint64_t)IWB * W) {
     // ---- lane j < IWB: read b0 + j -> slot j (errors and hand-offs leave here) ----
     const uint64_t ii = b0 + lane;
-    bool elig = false, hand = false;
+    bool elig = false, hand = false, route = false;
     uint64_t rr = 0;
     if (lane < IWB && ii < nsel) {
       GMeta mm;
@@ -1334,6 +1338,8 @@ __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, 
         R.status[mm.r] = mm.st, R.flags[mm.r] = 0;
       } else if (!wave_takes(L, B, mm, short_opl)) {
         hand = true;
+      } else if (LAG && routed.list && L.key_lag[mm.key * nd] == AM_LAG_ROUTED) {
+        route = true;  // a packed-routed key: the packed instantiation's (launch_split)
       } else {
         elig = true;
         ISlot &w = sl[lane];
@@ -1349,6 +1355,7 @@ __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, 
       base = uniform_u32(base);
       if (hand) next.list[base + (uint32_t)__popcll(hm & lt)] = (uint32_t)rr;
     }
+    if (LAG) retry_append(routed, route, (uint32_t)rr, lane);
     const uint64_t emask = __ballot(elig);
     wave_sync();
 
@@ -1477,14 +1484,14 @@ __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, 
         a.reset();
         __builtin_amdgcn_s_waitcnt(0);
         if (__ballot(escm == ~0ull)) {  // a long key's late tiles: the wave walks its escape marks
-          esc_pass_g<DMAX>(L, nd, u, off0, off1, stride, lane, ibm, a, LAG ? L.lag_ct : L.pk_vc);
+          esc_pass_g<DMAX>(L, nd, u, off0, off1, stride, lane, ibm, a, LAG ? L.lag_ct : L.pk_vc, LAG ? pk.K : NONE);
         } else {  // the lane's own escaped ops, marked by the tile loop: no second walk of the key
           for (uint64_t m = escm; m; m &= m - 1) {
             const uint32_t b = (uint32_t)__builtin_ctzll(m);
             const uint64_t p = t0 + (uint64_t)(b / OPL) * TILE + (uint64_t)lane * OPL + b % OPL;
             uint64_t sv[DMAX], ct;
             uint32_t meta;
-            esc_load<DMAX>(L, nd, stride, p, sv, ct, meta);
+            esc_load<DMAX>(L, nd, stride, p, LAG ? pk.K : NONE, sv, ct, meta);
             if (eval_op<DMAX, false>(u, meta, ct, sv, u.allmask, false, p, a) && !(meta & AM_META_BAD))
               atomicOr(&ibm[p >> 5], 1u << (p & 31));
           }
@@ -1777,7 +1784,7 @@ __global__ void __launch_bounds__(BLOCK) k_grp_row(am_op_log L, am_read_batch B,
       auto eval_full = [&](uint64_t p) -> bool {
         uint64_t svf[DMAX], ct;
         uint32_t meta;
-        esc_load<DMAX>(L, nd, stride, p, svf, ct, meta);  // (the columns when the op has no row)
+        esc_load<DMAX>(L, nd, stride, p, NONE, svf, ct, meta);  // (the columns when the op has no row)
         const uint32_t sp = (GENERAL && L.snap_pres) ? L.snap_pres[p] : u.allmask;
         const bool txm = GENERAL && u.has_txid && L.op_txid[p] == u.txid;
         return eval_op<DMAX, GENERAL>(u, meta, ct, svf, sp, txm, p, a) && !(meta & AM_META_BAD);
@@ -1878,12 +1885,20 @@ int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_rea
   const uint64_t bi = want_i < (uint64_t)ctx->n_cu * occ_i ? want_i : (uint64_t)ctx->n_cu * occ_i;
   const uint64_t bw = want_w < (uint64_t)ctx->n_cu * occ_w ? want_w : (uint64_t)ctx->n_cu * occ_w;
   if (bi == 0) return AM_OK;
-  if (lag)
+  if (lag) {
+    // the reads of packed-routed keys leave the lag instantiation through a list; the packed
+    // instantiation takes exactly those (an empty list: its blocks return at once)
+    am_retry routed;
+    am_sel rsel;
+    if (int rc = am_route_list(ctx, B->n_reads, &routed, &rsel)) return rc;
     hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, true>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B, *R,
-                       S, next, short_opl, (uint32_t *)ibm);
-  else
+                       S, next, routed, short_opl, (uint32_t *)ibm);
     hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B,
-                       *R, S, next, short_opl, (uint32_t *)ibm);
+                       *R, rsel, next, am_retry{}, short_opl, (uint32_t *)ibm);
+  } else {
+    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B,
+                       *R, S, next, am_retry{}, short_opl, (uint32_t *)ibm);
+  }
   hipLaunchKernelGGL((k_grp_recs<D, TYPE>), dim3((unsigned)bw), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S,
                      short_opl, (const uint32_t *)ibm);
   AM_HIP(hipGetLastError());

@@ -13,7 +13,7 @@
 
 #include "../../include/antidote_mat.h"
 
-enum { AM_SCR_PLAN = 0, AM_SCR_BIGMETA = 1, AM_SCR_BIGREC = 2, AM_SCR_ROWS = 3, AM_SCR_GRP = 4, AM_SCR_SPARE = 5, AM_SCR_SNAP = 6, AM_SCR_GC = 7, AM_SCR_SIZES = 8, AM_SCR_MISC = 9, AM_SCR_INCL = 10, AM_N_SCR = 11 };
+enum { AM_SCR_PLAN = 0, AM_SCR_BIGMETA = 1, AM_SCR_BIGREC = 2, AM_SCR_ROWS = 3, AM_SCR_GRP = 4, AM_SCR_SPARE = 5, AM_SCR_SNAP = 6, AM_SCR_GC = 7, AM_SCR_SIZES = 8, AM_SCR_MISC = 9, AM_SCR_INCL = 10, AM_SCR_ROUTE = 11, AM_N_SCR = 12 };
 
 struct am_ctx {
   int device = 0;
@@ -77,6 +77,12 @@ struct am_retry {
   uint32_t *list = nullptr;
   uint32_t *count = nullptr;
 };
+
+// The reads of packed-routed keys (include/antidote_mat.h AM_LAG_ROUTED) that a lag-view kernel
+// leaves to the packed instantiation of the same tier: an empty device list for up to n_reads
+// reads (`routed`, appended by the lag kernel) and the selection of exactly those reads (`sel`)
+// for the launch that follows on the same stream.  Valid until the next call on this context.
+int am_route_list(am_ctx *ctx, uint64_t n_reads, am_retry *routed, am_sel *sel);
 
 // scratch slot `slot` (0 planner, 1 big-read metadata, 2 big-read records): at least
 // `bytes` of device memory, valid until the next call for the same slot (stream-ordered

@@ -291,7 +291,7 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_g(am_op_log L, am_read_batch B,
         if (L.pk_vc[p] != AM_PK_ESC) continue;
         uint64_t sv[DMAX], ct;
         uint32_t meta;
-        esc_load<DMAX>(L, nd, stride, p, sv, ct, meta);
+        esc_load<DMAX>(L, nd, stride, p, NONE, sv, ct, meta);
         const uint32_t sp = L.snap_pres ? L.snap_pres[p] : u.allmask;
         const bool txm = u.has_txid && L.op_txid[p] == u.txid;
         if (!eval_op<DMAX, true>(u, meta, ct, sv, sp, txm, p, a)) continue;
@@ -432,6 +432,7 @@ struct QPre {
 struct QMeta {
   uint64_t key, off0, off1, K, rk0, rk1, ooff, o1, idb;
   uint32_t r, t, kt, kfl, G, ok;  // ok: i < nsel and key < n_keys
+  uint32_t lag0;                  // LAG: key_lag[key][0] (AM_LAG_ROUTED: a packed-routed key)
 };
 template <bool SEL>
 __device__ __forceinline__ QPre q_pre(const am_read_batch &B, const am_sel &S, uint32_t sel0, uint64_t nsel, uint64_t i) {
@@ -443,6 +444,7 @@ __device__ __forceinline__ QPre q_pre(const am_read_batch &B, const am_sel &S, u
   p.t = B.type[p.r];
   return p;
 }
+template <bool LAG>
 __device__ __forceinline__ QMeta q_meta(const am_op_log &L, const am_read_result &R, const QPre &p) {
   QMeta m;
   m.key = p.key, m.r = p.r, m.t = p.t;
@@ -459,6 +461,7 @@ __device__ __forceinline__ QMeta q_meta(const am_op_log &L, const am_read_result
   m.kt = L.key_type[k];
   m.kfl = (L.key_flags ? L.key_flags : L.key_type)[k];  // (key_type: a dummy, unused)
   m.K = L.key_tbase[k];
+  m.lag0 = LAG ? (uint32_t)L.key_lag[k * L.n_dc] : 0u;
   m.idb = (L.key_id_base ? L.key_id_base : L.key_off)[k];  // (key_off: a dummy, unused)
   // set fields for every read: the block's reads cover one span of each column, so the
   // lines are fetched whatever the types
@@ -478,9 +481,9 @@ __device__ __forceinline__ QMeta q_meta(const am_op_log &L, const am_read_result
 template <int DMAX, bool LAG>
 __device__ __forceinline__ QOwn q_publish(const am_op_log &L, const am_read_result &R, const ReadU<DMAX> &u,
                                           uint32_t nd, const QMeta &m, bool inb, uint32_t accept, am_retry next,
-                                          QSlot<DMAX> *slot, uint32_t lane, bool &any) {
+                                          am_retry routed, QSlot<DMAX> *slot, uint32_t lane, bool &any) {
   const uint64_t lt = (1ull << lane) - 1ull;
-  bool take = false, hand = false;
+  bool take = false, hand = false, route = false;
   if (inb) {
     int32_t st = AM_OK;
     if (!m.ok || m.t < AM_PN || m.t > AM_BCOUNTER) st = AM_ERR_INVALID;
@@ -489,7 +492,9 @@ __device__ __forceinline__ QOwn q_publish(const am_op_log &L, const am_read_resu
     if (st == AM_OK) {
       bool ok = ((accept >> m.t) & 1u) && m.off1 - (m.off0 & ~3ull) <= LBITS;
       if (ok && (m.t == AM_AWSET || m.t == AM_MVREG)) ok = m.G != AM_NGRP_NONE && m.G <= LGRP;
-      take = ok;
+      // a packed-routed key's read leaves through `routed`: the packed instantiation's (launch_d)
+      route = LAG && ok && routed.list && m.lag0 == (uint32_t)AM_LAG_ROUTED;
+      take = ok && !route;
       hand = !ok;
     } else {
       R.status[m.r] = st;
@@ -503,6 +508,7 @@ __device__ __forceinline__ QOwn q_publish(const am_op_log &L, const am_read_resu
     base = uniform_u32(base);
     if (hand) next.list[base + (uint32_t)__popcll(hm & lt)] = m.r;
   }
+  if (LAG) retry_append(routed, route, m.r, lane);
   const bool setr = m.t == AM_AWSET || m.t == AM_MVREG;
   const bool quad = take && m.off1 <= (m.off0 & ~3ull) + 16 && (!setr || (L.gmask && m.G <= AM_GMASK_MAX_GRP));
   // scan position: quad reads by type, then the lane-finished reads, then the rest
@@ -600,7 +606,7 @@ __device__ __forceinline__ void q_lww(uint32_t ib, u32x4 e0, u32x4 e1, u32x4 e2,
 #endif
 template <int DMAX, bool SEL, bool LAG>
 __global__ void __launch_bounds__(LBLOCK) k_lane_q(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
-                                                   am_retry next, uint32_t accept) {
+                                                   am_retry next, am_retry routed, uint32_t accept) {
   constexpr int NPH = qph<DMAX>();
   __shared__ QSmem<DMAX> smem[LBLOCK / WAVE];
   QSmem<DMAX> &sm = smem[threadIdx.x / WAVE];
@@ -619,17 +625,17 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_q(am_op_log L, am_read_batch B,
   QSlot<DMAX> *const slot = sm.slot;
   QPre pn = q_pre<SEL>(B, S, sel0, nsel, first + step + lane);
   bool any = false;
-  QOwn own = q_publish<DMAX, LAG>(L, R, u, nd, q_meta(L, R, q_pre<SEL>(B, S, sel0, nsel, first + lane)),
-                             first + lane < nsel, accept, next, slot, lane, any);
+  QOwn own = q_publish<DMAX, LAG>(L, R, u, nd, q_meta<LAG>(L, R, q_pre<SEL>(B, S, sel0, nsel, first + lane)),
+                             first + lane < nsel, accept, next, routed, slot, lane, any);
   wave_sync();
   PH_DECL();
   PH_BEGIN();
   for (uint64_t b0 = first; b0 < nsel; b0 += step) {
     QMeta m;
     if (!any) {
-      m = q_meta(L, R, pn);
+      m = q_meta<LAG>(L, R, pn);
       pn = q_pre<SEL>(B, S, sel0, nsel, b0 + 2 * step + lane);
-      own = q_publish<DMAX, LAG>(L, R, u, nd, m, b0 + step + lane < nsel, accept, next, slot, lane, any);
+      own = q_publish<DMAX, LAG>(L, R, u, nd, m, b0 + step + lane < nsel, accept, next, routed, slot, lane, any);
       wave_sync();
       PH(5);
       continue;
@@ -671,7 +677,7 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_q(am_op_log L, am_read_batch B,
         }
       }
       if (pg == 0) {  // the next block's metadata, behind this block's scan loads
-        m = q_meta(L, R, pn);
+        m = q_meta<LAG>(L, R, pn);
         pn = q_pre<SEL>(B, S, sel0, nsel, b0 + 2 * step + lane);
       }
 #pragma unroll
@@ -774,7 +780,7 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_q(am_op_log L, am_read_batch B,
     // the next block's reads: statuses, hand-offs, positions (its metadata has arrived by now;
     // the slots are free once scanned)
     wave_sync();
-    own = q_publish<DMAX, LAG>(L, R, u, nd, m, b0 + step + lane < nsel, accept, next, slot, lane, any);
+    own = q_publish<DMAX, LAG>(L, R, u, nd, m, b0 + step + lane < nsel, accept, next, routed, slot, lane, any);
     wave_sync();
     PH(1);
 
@@ -832,7 +838,7 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_q(am_op_log L, am_read_batch B,
       auto esc_op = [&](uint64_t p) {
         uint64_t sv[DMAX], ct;
         uint32_t meta;
-        esc_load<DMAX>(L, nd, stride, p, sv, ct, meta);
+        esc_load<DMAX>(L, nd, stride, p, K, sv, ct, meta);
         if (!eval_op<DMAX, false>(u, meta, ct, sv, u.allmask, false, p, a)) return;
         if (scal) {
           if (t == AM_PN) pv.add(L.p0[p], 0);
@@ -904,12 +910,23 @@ int launch_dl(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_read_r
   if (blocks == 0) return AM_OK;
   if (general)
     hipLaunchKernelGGL((k_lane_g<D>), dim3((unsigned)blocks), dim3(LBLOCK), 0, ctx->stream, *L, *B, *R, S, next, accept);
-  else if (S.idx)
-    hipLaunchKernelGGL((k_lane_q<D, true, LAG>), dim3((unsigned)blocks), dim3(LBLOCK), 0, ctx->stream, *L, *B, *R, S,
-                       next, accept);
-  else
-    hipLaunchKernelGGL((k_lane_q<D, false, LAG>), dim3((unsigned)blocks), dim3(LBLOCK), 0, ctx->stream, *L, *B, *R, S,
-                       next, accept);
+  else {
+    // the lag instantiation leaves the reads of packed-routed keys in a list; the packed
+    // instantiation takes exactly those (an empty list: its blocks return at once)
+    am_retry routed;
+    am_sel rsel;
+    if (LAG)
+      if (int rc = am_route_list(ctx, B->n_reads, &routed, &rsel)) return rc;
+    if (S.idx)
+      hipLaunchKernelGGL((k_lane_q<D, true, LAG>), dim3((unsigned)blocks), dim3(LBLOCK), 0, ctx->stream, *L, *B, *R, S,
+                         next, routed, accept);
+    else
+      hipLaunchKernelGGL((k_lane_q<D, false, LAG>), dim3((unsigned)blocks), dim3(LBLOCK), 0, ctx->stream, *L, *B, *R,
+                         S, next, routed, accept);
+    if (LAG)
+      hipLaunchKernelGGL((k_lane_q<D, true, false>), dim3((unsigned)blocks), dim3(LBLOCK), 0, ctx->stream, *L, *B, *R,
+                         rsel, next, am_retry{}, accept);
+  }
   AM_HIP(hipGetLastError());
   return AM_OK;
 }

@@ -235,8 +235,52 @@ int build_esc_rows(am_store *st) {
 
 // ---- the lag view (am_op_log.lag_ct / lag / key_lag) from the packed view: one wave per key.
 //      Pass 1: key_lag[k][d] = min over the key's packed ops of (ct - X[d]) = entry(dc) - entry(d);
-//      pass 2: each op's commit entry and lags, or AM_PK_ESC when a lag exceeds 16 bits ----
+//      pass 2: each op's commit entry and lags, or AM_PK_ESC when a lag exceeds 16 bits (a
+//      lag-only escape: the op is in the packed view);
+//      pass 3: the key's routing (include/antidote_mat.h AM_LAG_ROUTED): when its lag-only
+//      escapes exceed AM_LAG_ROUTE_NUM / AM_LAG_ROUTE_DEN of its packed ops, or a lag base
+//      does not fit int32, key_lag[k][0] = AM_LAG_ROUTED and every op's lag_ct = AM_PK_ESC:
+//      readers stream the key's packed view instead of walking its escapes op by op ----
 constexpr uint32_t LAG_MAX_DC = 16;
+
+// one key's lag classification, shared by the builder and the counters (am_store_view_stats)
+struct LagKey {
+  int64_t lb[LAG_MAX_DC];  // lag bases
+  bool fit;                // every lag base within (INT32_MIN, INT32_MAX]
+};
+__device__ __forceinline__ void lag_bases(const am_op_log &L, uint64_t stride, uint64_t o0, uint64_t o1, uint32_t lane,
+                                          LagKey &lk) {
+  lk.fit = true;
+  for (uint32_t d = 0; d < L.n_dc; ++d) {
+    uint64_t m = ~0ull;  // min of (ct - X[d]) + 2^32 (biased: the difference lies in (-2^32, 2^32))
+    for (uint64_t p = o0 + lane; p < o1; p += WAVE) {
+      if (L.pk_vc[p] == AM_PK_ESC) continue;
+      const uint32_t c = L.pk_vc[(uint64_t)AM_META_DC(L.op_meta[p]) * stride + p];
+      const uint64_t v = (uint64_t)c + (1ull << 32) - L.pk_vc[(uint64_t)d * stride + p];
+      m = v < m ? v : m;
+    }
+    m = wave_min_u64(m);
+    lk.lb[d] = m == ~0ull ? 0 : (int64_t)m - (int64_t)(1ull << 32);
+    lk.fit &= lk.lb[d] > INT32_MIN && lk.lb[d] <= INT32_MAX;  // (INT32_MIN is the routing mark)
+  }
+}
+// op p of the packed view (pk_vc[p] != AM_PK_ESC): its lags under the key's bases, all within 16 bits?
+template <class Out>
+__device__ __forceinline__ bool lag_op(const am_op_log &L, uint64_t stride, uint64_t p, const LagKey &lk, uint32_t &c,
+                                       Out out) {
+  c = L.pk_vc[(uint64_t)AM_META_DC(L.op_meta[p]) * stride + p];
+  bool ok = lk.fit;
+  for (uint32_t d = 0; d < L.n_dc; ++d) {
+    const int64_t l = ok ? (int64_t)c - (int64_t)L.pk_vc[(uint64_t)d * stride + p] - lk.lb[d] : 0;
+    ok = ok && l >= 0 && l <= 0xFFFF;
+    out(d, (uint16_t)(ok ? l : 0));
+  }
+  return ok;
+}
+__device__ __forceinline__ bool lag_routed(uint64_t n_packed, uint64_t n_lag_only, bool fit) {
+  return n_packed && (!fit || n_lag_only * AM_LAG_ROUTE_DEN > n_packed * AM_LAG_ROUTE_NUM);
+}
+
 __global__ void k_lag(am_op_log L, uint32_t *lag_ct, uint16_t *lag, int32_t *key_lag) {
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / WAVE);
@@ -244,31 +288,56 @@ __global__ void k_lag(am_op_log L, uint32_t *lag_ct, uint16_t *lag, int32_t *key
   const uint32_t nd = L.n_dc;
   for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; k < L.n_keys; k += waves) {
     const uint64_t o0 = L.key_off[k], o1 = am_kend(L, k);
-    int64_t lb[LAG_MAX_DC];
-    bool fit = true;  // every lag base within int32
-    for (uint32_t d = 0; d < nd; ++d) {
-      uint64_t m = ~0ull;  // min of (ct - X[d]) + 2^32 (biased: the difference lies in (-2^32, 2^32))
-      for (uint64_t p = o0 + lane; p < o1; p += WAVE) {
-        if (L.pk_vc[p] == AM_PK_ESC) continue;
-        const uint32_t c = L.pk_vc[(uint64_t)AM_META_DC(L.op_meta[p]) * stride + p];
-        const uint64_t v = (uint64_t)c + (1ull << 32) - L.pk_vc[(uint64_t)d * stride + p];
-        m = v < m ? v : m;
-      }
-      m = wave_min_u64(m);
-      lb[d] = m == ~0ull ? 0 : (int64_t)m - (int64_t)(1ull << 32);
-      fit &= lb[d] >= INT32_MIN && lb[d] <= INT32_MAX;
-      if (lane == 0) key_lag[k * nd + d] = fit ? (int32_t)lb[d] : 0;
-    }
+    LagKey lk;
+    lag_bases(L, stride, o0, o1, lane, lk);
+    uint32_t npk = 0, nlo = 0;  // this lane's packed ops, and its lag-only escapes
     for (uint64_t p = o0 + lane; p < o1; p += WAVE) {
-      bool ok = fit && L.pk_vc[p] != AM_PK_ESC;
-      const uint32_t c = ok ? L.pk_vc[(uint64_t)AM_META_DC(L.op_meta[p]) * stride + p] : 0u;
-      for (uint32_t d = 0; d < nd; ++d) {
-        const int64_t l = ok ? (int64_t)c - (int64_t)L.pk_vc[(uint64_t)d * stride + p] - lb[d] : 0;
-        ok = ok && l >= 0 && l <= 0xFFFF;
-        lag[(uint64_t)d * stride + p] = (uint16_t)(ok ? l : 0);
-      }
+      const bool pk = L.pk_vc[p] != AM_PK_ESC;
+      uint32_t c = 0;
+      bool ok = false;
+      if (pk) ok = lag_op(L, stride, p, lk, c, [&](uint32_t d, uint16_t l) { lag[(uint64_t)d * stride + p] = l; });
+      if (!ok)
+        for (uint32_t d = 0; d < nd; ++d) lag[(uint64_t)d * stride + p] = 0;
       lag_ct[p] = ok ? c : AM_PK_ESC;
+      npk += pk, nlo += pk && !ok;
     }
+    const bool routed = lag_routed(wave_sum_u32(npk), wave_sum_u32(nlo), lk.fit);
+    if (routed)
+      for (uint64_t p = o0 + lane; p < o1; p += WAVE) lag_ct[p] = AM_PK_ESC;
+    for (uint32_t d = lane; d < nd; d += WAVE)
+      key_lag[k * nd + d] = routed && d == 0 ? AM_LAG_ROUTED : (lk.fit ? (int32_t)lk.lb[d] : 0);
+  }
+}
+
+// ---- am_store_view_stats: the counters from the store's current views, one wave per key ----
+__global__ void k_view_stats(am_op_log L, unsigned long long *out) {
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / WAVE);
+  const uint64_t stride = L.snap_stride ? L.snap_stride : L.n_ops;
+  const bool lagv = L.lag_ct && L.lag && L.key_lag && L.n_dc <= LAG_MAX_DC;
+  uint64_t ops = 0, esc = 0, lonly = 0, rkeys = 0, rops = 0;  // lane 0's sums
+  for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; k < L.n_keys; k += waves) {
+    const uint64_t o0 = L.key_off[k], o1 = am_kend(L, k);
+    const bool routed = lagv && o1 > o0 && L.key_lag[k * L.n_dc] == AM_LAG_ROUTED;
+    LagKey lk;
+    if (routed) lag_bases(L, stride, o0, o1, lane, lk);  // the marked row no longer holds them
+    uint32_t ne = 0, nl = 0;
+    for (uint64_t p = o0 + lane; p < o1; p += WAVE) {
+      const bool pk = !L.pk_vc || L.pk_vc[p] != AM_PK_ESC;  // (no packed view: nothing escapes it)
+      ne += !pk;
+      uint32_t c;
+      if (routed) nl += pk && !lag_op(L, stride, p, lk, c, [](uint32_t, uint16_t) {});
+      else nl += lagv && pk && L.lag_ct[p] == AM_PK_ESC;
+    }
+    ops += o1 - o0, esc += wave_sum_u32(ne), lonly += wave_sum_u32(nl);
+    rkeys += routed, rops += routed ? o1 - o0 : 0;
+  }
+  if (lane == 0) {
+    atomicAdd(out + AM_VIEW_STAT_OPS, (unsigned long long)ops);
+    atomicAdd(out + AM_VIEW_STAT_PK_ESC, (unsigned long long)esc);
+    atomicAdd(out + AM_VIEW_STAT_LAG_ONLY_ESC, (unsigned long long)lonly);
+    atomicAdd(out + AM_VIEW_STAT_ROUTED_KEYS, (unsigned long long)rkeys);
+    atomicAdd(out + AM_VIEW_STAT_ROUTED_OPS, (unsigned long long)rops);
   }
 }
 
@@ -574,6 +643,23 @@ int am_store_pack_records(am_store *st) {
   if (int rc = build_esc_rows(st)) return rc;
   if (int rc = build_lag(st)) return rc;
   return build_zones(st, st->zone_level);
+}
+
+// the view counters of a store, computed from its current views (true after am_store_apply)
+extern "C" int am_store_view_stats(am_ctx *c, const am_store *st, uint64_t *out) {
+  if (!c || !st || st->ctx != c || !out) return AM_ERR_INVALID;
+  AM_LOCK(c);
+  AM_HIP(hipSetDevice(c->device));
+  for (int i = 0; i < AM_VIEW_STAT_N; ++i) out[i] = 0;
+  const am_op_log &d = st->dev;
+  if (!d.n_keys || !d.key_off) return AM_OK;
+  void *cnt = nullptr;
+  if (int rc = am_ctx_scratch(c, AM_SCR_MISC, 256, &cnt)) return rc;
+  AM_HIP(hipMemsetAsync(cnt, 0, AM_VIEW_STAT_N * 8, c->stream));
+  const uint64_t blocks = (d.n_keys + 3) / 4 < 65536 ? (d.n_keys + 3) / 4 : 65536;
+  hipLaunchKernelGGL(k_view_stats, dim3((unsigned)blocks), dim3(256), 0, c->stream, d, (unsigned long long *)cnt);
+  AM_HIP(hipGetLastError());
+  return am_ctx_fetch(c, cnt, AM_VIEW_STAT_N, out);
 }
 
 // drop the store's zone index and rebuild it at `level`

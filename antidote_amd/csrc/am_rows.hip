@@ -271,7 +271,7 @@ __global__ void __launch_bounds__(BLOCK) k_rows(am_op_log L, am_read_batch B, am
           } else {
             uint64_t ct, sv[DMAX];
             if (PACKED) {  // rare: the op does not fit the packed view
-              esc_load<DMAX>(L, nd, stride, p, sv, ct, meta);
+              esc_load<DMAX>(L, nd, stride, p, NONE, sv, ct, meta);
             } else {
               ct = cur.w;
 #pragma unroll

@@ -144,6 +144,18 @@ int am_ctx_scratch(am_ctx *c, int slot, size_t bytes, void **out) {
   return AM_OK;
 }
 
+// layout: words 0, 1 = the selection's range {0, count}; the list from word 4 (16-byte aligned)
+int am_route_list(am_ctx *c, uint64_t n_reads, am_retry *routed, am_sel *sel) {
+  void *p = nullptr;
+  if (int rc = am_ctx_scratch(c, AM_SCR_ROUTE, (n_reads + 68) * sizeof(uint32_t), &p)) return rc;
+  // (the first list words too: a kernel's lanes past the selection read entry 0 as a dummy)
+  AM_HIP(hipMemsetAsync(p, 0, 32, c->stream));
+  uint32_t *w = (uint32_t *)p;
+  routed->count = w + 1, routed->list = w + 4;
+  sel->range = w, sel->idx = w + 4;
+  return AM_OK;
+}
+
 int am_ctx_fetch(am_ctx *c, const void *dev, uint32_t n, uint64_t *host) {
   AM_LOCK(c);
   if (n > 64) return AM_ERR_INVALID;

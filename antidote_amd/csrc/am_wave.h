@@ -189,6 +189,17 @@ __device__ __forceinline__ uint32_t shfl_u32(uint32_t v, uint32_t src) {
   return (uint32_t)__shfl((int)v, (int)src, WAVE);
 }
 
+// appends r to the device list q (one atomic per wave) for the lanes with `put`; every lane of
+// the wave in the call
+__device__ __forceinline__ void retry_append(am_retry q, bool put, uint32_t r, uint32_t lane) {
+  const uint64_t m = __ballot(put);
+  if (!m) return;
+  uint32_t base = 0;
+  if (lane == 0) base = atomicAdd(q.count, (uint32_t)__popcll(m));
+  base = uniform_u32(base);
+  if (put) q.list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = r;
+}
+
 // ---- per-read uniform inputs and per-lane accumulators ----
 template <int DMAX>
 struct ReadU {
@@ -313,10 +324,25 @@ __device__ __forceinline__ const uint64_t *esc_row(const am_op_log &L, uint64_t 
   const uint32_t ri = L.pk_vc[stride + p];
   return ri ? L.esc_rows + (uint64_t)(ri - 1) * (2 + L.n_dc) : nullptr;
 }
-// commit time, meta byte and snapshot entries of escaped op p: one row, or the op columns
+// commit time, meta byte and snapshot entries of op p, escaped from the view its read streamed.
+// Two levels: an op the packed view holds (a lag-only escape: lag_ct[p] == AM_PK_ESC but
+// pk_vc[p] is an entry) is rebuilt from its nd u32 packed entries, X[d] = K + entry, K the
+// key's time base (K == NONE: the caller has none -- a full-view read); an op escaped from the
+// packed view reads its escape row, or the op columns.
 template <int DMAX>
-__device__ __forceinline__ void esc_load(const am_op_log &L, uint32_t nd, uint64_t stride, uint64_t p,
+__device__ __forceinline__ void esc_load(const am_op_log &L, uint32_t nd, uint64_t stride, uint64_t p, uint64_t K,
                                          uint64_t (&sv)[DMAX], uint64_t &ct, uint32_t &meta) {
+  if (K != NONE && L.pk_vc && L.pk_vc[p] != AM_PK_ESC) {
+    meta = L.op_meta[p];
+    const uint32_t dc = meta & 31u;
+    ct = 0;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) {
+      sv[d] = d < (int)nd ? K + L.pk_vc[(uint64_t)d * stride + p] : 0;
+      ct = (uint32_t)d == dc ? sv[d] : ct;
+    }
+    return;
+  }
   if (const uint64_t *w = esc_row(L, stride, p)) {
     ct = w[0], meta = (uint32_t)w[1];
 #pragma unroll
@@ -419,7 +445,9 @@ struct LagRead {
 };
 template <int DMAX>
 __device__ __forceinline__ void lag_setup(const am_op_log &L, uint32_t nd, uint64_t key, bool on, LagRead<DMAX> &lr) {
-  lr.on = on;
+  // a packed-routed key (AM_LAG_ROUTED in its row) streams the packed view: lr.on false
+  lr.on = on && uniform_u32((uint32_t)L.key_lag[key * nd]) != (uint32_t)AM_LAG_ROUTED;
+  on = lr.on;
 #pragma unroll
   for (int d = 0; d < DMAX; ++d) lr.lb[d] = on && d < (int)nd ? uniform_u32((uint32_t)L.key_lag[key * nd + d]) : 0u;
 }
@@ -505,7 +533,7 @@ __device__ __forceinline__ uint32_t incl4(const am_op_log &L, uint32_t nd, uint6
     if (PACKED && L.pk_vc[p] != AM_PK_ESC) continue;
     uint64_t sv[DMAX], ct;
     uint32_t meta;
-    esc_load<DMAX>(L, nd, stride, p, sv, ct, meta);
+    esc_load<DMAX>(L, nd, stride, p, NONE, sv, ct, meta);  // (packed-view escapes only reach here)
     const uint32_t sp = L.snap_pres ? L.snap_pres[p] : u.allmask;
     if (eval_op<DMAX, true>(u, meta, ct, sv, sp, u.has_txid && tx[k] == u.txid, p, a)) ib |= 1u << k;
   }

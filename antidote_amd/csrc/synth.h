@@ -14,6 +14,8 @@
 //                   snap_vc[commit_dc] < commit_time as ClockSI guarantees)
 //   read clock(q) = BASE + floor(q * N) * STEP + d * STEP/2   per DC d
 //   (esc_ppm > 0: a fraction of ops carry one remote DC's entry 2^33 us behind, am_syn_snap_e)
+//   (gst_ppm > 0: a fraction of keys carry the reference's stable-snapshot cadence in their
+//    remote entries -- 0.1-1.2 s behind the commit, in steps of 1 s -- am_syn_snap_g below)
 // Payloads:
 //   PN   delta uniform in [-1000, 1000]
 //   LWW  ts = BASE + perm_k(i) * STEP + jitter  (perm_k a bijection of [0, 2^ceil(log2 N)),
@@ -70,6 +72,40 @@ AM_HD uint64_t am_syn_snap_e(uint64_t seed, uint64_t key, uint64_t i, uint32_t d
   const uint32_t cdc = (uint32_t)(am_syn_h(seed, key, i, 1) % n_dc);  // am_syn_dc
   const uint32_t ed = (cdc + 1u + (uint32_t)(am_syn_h(seed, key, i, 61) % (n_dc - 1))) % n_dc;
   return d == ed ? s - AM_SYN_ESC_LAG : s;
+}
+
+// GST-cadence clocks (gst_ppm > 0): a key is a GST key iff h(key,0,72) mod 10^6 < gst_ppm, and
+// the remote entries of its ops come from the commit DC's stable snapshot instead of trailing
+// the commit by milliseconds.  The coordinator starts a transaction from the stable snapshot
+// with only its own DC's entry replaced by the local clock
+// (src/clocksi_interactive_coord.erl:905-910); the stable snapshot is re-merged every
+// META_DATA_SLEEP = 1000 ms from partition clocks pushed every 100 ms
+// (include/antidote.hrl:55-60).  So with t0 the op's own-DC entry (the transaction start,
+// am_syn_snap) and c its commit DC, the entry of a remote DC d is
+//   stable(c,d,t0) = phi + floor((t0 - phi) / P) * P - delta,   P = 10^6 us,
+//   phi = h(c,d,70) mod P,   delta = 10^5 + h(c,d,71) mod 10^5:
+// phi (the merge phase) and delta (the pushed clocks' age at the merge) depend on (seed, c, d)
+// only -- a DC's stable snapshot is DC-wide, not per key.  commit_time - X[d] then lies in
+// [10^5, 1.2 * 10^6 + (max_lag + 1) * STEP) and for fixed (c, d) the entries take at most
+// floor(T / P) + 2 distinct values over a span T.  esc_ppm composes on top.
+#define AM_SYN_GST_P 1000000ull
+AM_HD bool am_syn_gst_key(uint64_t seed, uint64_t key, uint32_t gst_ppm) {
+  return gst_ppm && am_syn_h(seed, key, 0, 72) % 1000000u < gst_ppm;
+}
+AM_HD uint64_t am_syn_stable(uint64_t seed, uint32_t c, uint32_t d, uint64_t t0) {
+  const uint64_t phi = am_syn_h(seed, c, d, 70) % AM_SYN_GST_P;
+  const uint64_t delta = 100000ull + am_syn_h(seed, c, d, 71) % 100000ull;
+  return phi + (t0 - phi) / AM_SYN_GST_P * AM_SYN_GST_P - delta;
+}
+// snapshot entry d of op i: am_syn_snap_e, with the remote entries of a GST key's ops stepped
+AM_HD uint64_t am_syn_snap_g(uint64_t seed, uint64_t key, uint64_t i, uint32_t d, uint32_t max_lag, uint32_t n_dc,
+                             uint32_t esc_ppm, uint32_t gst_ppm) {
+  const uint64_t e = am_syn_snap_e(seed, key, i, d, max_lag, n_dc, esc_ppm);
+  if (!am_syn_gst_key(seed, key, gst_ppm)) return e;
+  const uint32_t c = (uint32_t)(am_syn_h(seed, key, i, 1) % n_dc);  // am_syn_dc
+  if (d == c) return e;
+  const uint64_t s = am_syn_snap(seed, key, i, d, max_lag);
+  return am_syn_stable(seed, c, d, am_syn_snap(seed, key, i, c, max_lag)) - (s - e);  // s - e: the escape lag
 }
 
 AM_HD uint64_t am_syn_read_clock(uint64_t n_ops_per_key, double q, uint32_t d) {

@@ -89,6 +89,13 @@ class Store:
         _ZONES bounds only, _EXACT + exact marks, _SUMMARIES + group summaries, the default)."""
         abi.check(self.mat.L.am_store_index(self.mat.ctx, self.handle, int(level)), "am_store_index")
 
+    def view_stats(self) -> Dict[str, int]:
+        """Counters of the store's views as they are now (am_store_view_stats): ops, ops escaped
+        from the packed view, lag-only escaped ops, packed-routed keys and their ops."""
+        out = (ctypes.c_uint64 * abi.AM_VIEW_STAT_N)()
+        abi.check(self.mat.L.am_store_view_stats(self.mat.ctx, self.handle, out), "am_store_view_stats")
+        return dict(zip(abi.VIEW_STATS, (int(x) for x in out)))
+
     def reserve(self) -> "Store":
         """A copy with room for appends per key (am_store_reserve), the layout am_store_apply
         updates in place."""

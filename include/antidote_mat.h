@@ -72,7 +72,7 @@
 extern "C" {
 #endif
 
-#define AM_ABI_VERSION 12
+#define AM_ABI_VERSION 13
 #define AM_MAX_DC 32
 
 /* CRDT types (the reference's type atoms) */
@@ -250,15 +250,28 @@ typedef struct am_op_log {
    * lags, e.g. behind a partition) or an invalid effect. */
   const uint64_t *esc_rows;    /* [n_esc][2 + n_dc] or NULL                           */
   /* Lag view (device stores with the packed view, n_dc <= 16, or NULL): an op's commit vector
-   * as its commit time and one 16-bit lag per DC -- the snapshot entries of a transaction trail
-   * its commit by milliseconds -- so the inclusion test streams 4 + 2 * n_dc bytes per op instead
-   * of 4 * n_dc (20 B at D = 8, not 32):
+   * as its commit time and one 16-bit lag per DC, so the inclusion test streams 4 + 2 * n_dc
+   * bytes per op instead of 4 * n_dc (20 B at D = 8, not 32):
    *   lag_ct[p]     = commit_time - key_tbase[k]   (u32), or AM_PK_ESC when the op is escaped
    *                   from the packed view or one of its lags does not fit
    *   lag[d][p]     = (commit_time - X[d]) - key_lag[k][d]   in [0, 0xFFFF]   (X[dc] = ct: lag 0)
-   *   key_lag[k][d] = the smallest commit_time - X[d] over the key's fitting ops (int32)
-   * so X[d] - key_tbase[k] = lag_ct[p] - key_lag[k][d] - lag[d][p].  Maintained by every writer
-   * (am_store_apply rewrites a touched key's columns and its key_lag row). */
+   *   key_lag[k][d] = the smallest commit_time - X[d] over the key's packed ops (int32)
+   * so X[d] - key_tbase[k] = lag_ct[p] - key_lag[k][d] - lag[d][p].  Lags fit when a
+   * transaction's snapshot entries trail its commit within a 65 ms band per (key, DC); the
+   * reference's remote entries come from the stable snapshot, 0.1-1.2 s behind in 1 s steps
+   * (src/clocksi_interactive_coord.erl:905-910), and do not.  Hence two rules.
+   * Reader contract:
+   *  - Two-level escape.  lag_ct[p] == AM_PK_ESC says only that the lag view does not hold op p.
+   *    If pk_vc[0][p] != AM_PK_ESC (a lag-only escape) the op is evaluated from its packed entries
+   *    X[d] = key_tbase[k] + pk_vc[d][p]; only an op escaped from the packed view reads its escape
+   *    row or the full columns.
+   *  - Routing.  A key whose lag-only escapes exceed AM_LAG_ROUTE_NUM / AM_LAG_ROUTE_DEN of its
+   *    packed ops, or whose lag bases do not fit (INT32_MIN, INT32_MAX], is packed-routed: key_lag[k][0] ==
+   *    AM_LAG_ROUTED, every lag_ct of the key is AM_PK_ESC, and the rest of its key_lag row and
+   *    its lag columns are unspecified.  Readers test the mark before using the row and stream
+   *    the key's packed view.
+   * Maintained by every writer (am_store_apply rewrites a touched key's columns and its key_lag
+   * row, mark included, and sets lag_ct = AM_PK_ESC on the slots a shrunk key frees). */
   const uint32_t *lag_ct;      /* [snap_stride]                                       */
   const uint16_t *lag;         /* [n_dc][snap_stride]                                 */
   const int32_t *key_lag;      /* [n_keys][n_dc]                                      */
@@ -289,6 +302,10 @@ typedef struct am_op_log {
 #define AM_BREC_KILL (1u << 10)
 #define AM_BREC_GRP(m) ((m) >> 11)
 #define AM_PK_ESC 0xFFFFFFFFu
+/* the packed-routed mark of a key (key_lag[k][0]) and the routing share */
+#define AM_LAG_ROUTED INT32_MIN
+#define AM_LAG_ROUTE_NUM 1u
+#define AM_LAG_ROUTE_DEN 8u
 
 /*
  * CRDT values (base snapshots in, materialized values out), SoA over reads.
@@ -396,6 +413,16 @@ int am_store_destroy(am_store *st);
 #define AM_INDEX_EXACT 2
 #define AM_INDEX_SUMMARIES 3
 int am_store_index(am_ctx *ctx, am_store *st, int level);
+/* Counters of the store's views, computed by a kernel over the views as they are now (not
+ * cached: true after am_store_apply); blocks until done.  A store without a lag view reports
+ * zeros for the last three. */
+#define AM_VIEW_STAT_OPS 0           /* ops in the store                                      */
+#define AM_VIEW_STAT_PK_ESC 1        /* ops escaped from the packed view                      */
+#define AM_VIEW_STAT_LAG_ONLY_ESC 2  /* ops in the packed view with a lag that does not fit   */
+#define AM_VIEW_STAT_ROUTED_KEYS 3   /* packed-routed keys (key_lag[k][0] == AM_LAG_ROUTED)   */
+#define AM_VIEW_STAT_ROUTED_OPS 4    /* ops of those keys                                     */
+#define AM_VIEW_STAT_N 5
+int am_store_view_stats(am_ctx *ctx, const am_store *st, uint64_t out[AM_VIEW_STAT_N]);
 
 /* ---- the hot path ---- */
 /* Device pointers; runs on the ctx stream.  Asynchronous except for two data-dependent
@@ -687,7 +714,9 @@ typedef struct am_synth_params {
                             am_key_partition(key, 64) = key mod 64 is in the mask */
   uint32_t esc_ppm;      /* ops (per 10^6) whose snapshot_time holds one remote DC's entry
                             2^33 us behind: outside the packed view's window (escaped ops) */
-  uint32_t _pad2;
+  uint32_t gst_ppm;      /* keys (per 10^6) whose ops carry the reference's stable-snapshot cadence:
+                            remote entries 0.1-1.2 s behind the commit, in 1 s steps (synth.h
+                            am_syn_snap_g); 0: every entry trails its commit by milliseconds */
 } am_synth_params;
 #define AM_SYNTH_MV_BC 6
 /* Device log owned by the returned store. */
