@@ -22,8 +22,8 @@
 //     its slot is the rank's set bit of the bitmap, its value the sum;
 //   * the scalar outputs go through LDS to the read's lane and leave with one coalesced store
 //     per column; the next read's first window is loaded while a read is evaluated.
-// Ops outside the views are evaluated from their escape rows or the full columns by the row,
-// one DC per lane.  Reads it does not take (> BCR_OPS ops) go to `next`.
+// Ops outside the streamed view are evaluated through the escape reader (am_wave.h EscOp) by the
+// row, one DC per lane.  Reads it does not take (> BCR_OPS ops) go to `next`.
 #include "am_block.h"
 
 using namespace amk;
@@ -268,14 +268,9 @@ __global__ void __launch_bounds__(BLOCK, AM_BCR_WAVES) k_bc_rows(am_op_log L, am
           const uint32_t t = (uint32_t)__builtin_ctz(tb);
           const uint64_t p = a0 + (uint64_t)RG * t + owner;
           const uint32_t q = (uint32_t)(p - in.off0);
-          // a lag-only escape (the packed view holds the op): lane d's packed entry, K + entry;
-          // else its escape row, or the columns
-          const bool pkd = LAG && L.pk_vc[p] != AM_PK_ESC;
-          const uint64_t *w = pkd ? nullptr : esc_row(L, stride, p);
-          const uint32_t meta = w ? (uint32_t)w[1] : L.op_meta[p], dc = meta & 31u;
-          uint64_t xd = 0;
-          if (sl < nd && pkd) xd = in.K + L.pk_vc[(uint64_t)sl * stride + p];
-          else if (sl < nd) xd = sl == dc ? (w ? w[0] : L.commit_time[p]) : (w ? w[2 + sl] : L.snap_vc[(uint64_t)sl * stride + p]);
+          const EscOp e = esc_open(L, stride, p, LAG ? in.K : NONE);
+          const uint32_t meta = e.meta;
+          const uint64_t xd = sl < nd ? e.x(sl) : 0;  // lane d: X[d]
           const bool failx = sl < nd && (!((u.spres >> sl) & 1u) || xd > vS);
           const bool included = row_or_u32(failx ? 1u : 0u) == 0;
           if (sl == 0) fl |= miss;

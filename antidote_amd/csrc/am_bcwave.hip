@@ -10,7 +10,7 @@
 //   * slots start at the base value (bc_base: row r of the base arrays, or a snapshot-cache
 //     entry in the value pool);
 //   * the read's ops stream in 256-op tiles over the packed view (am_wave.h incl4; escaped
-//     ops from the full columns), payload words loaded with them (16-byte loads);
+//     ops through the escape reader, EscOp), payload words loaded with them (16-byte loads);
 //   * every included amount goes into its slot with an exact 128-bit LDS accumulation
 //     (64-bit atomics + carry, am_block.h acc128_atomic) and sets the slot's presence;
 //   * scalar outputs come from wave reductions, the slots leave with coalesced stores and an
@@ -57,8 +57,8 @@ __device__ __forceinline__ void bc_inputs(const am_op_log &L, const am_read_batc
 
 // GENERAL false (the batch clock, no bases / TxIds / op presence): the clock is read once per
 // wave and the tile loop tests the packed entries only; escaped ops (outside the packed view)
-// are evaluated from the full columns in a pass of their own after the loop, so the loop holds
-// neither the base thresholds nor the full-width accumulators (C5: 252 -> fewer VGPRs).
+// are evaluated through the escape reader (EscOp) in a pass of their own after the loop, so the
+// loop holds neither the base thresholds nor the full-width accumulators (C5: 252 -> fewer VGPRs).
 template <int DMAX, bool GENERAL>
 __global__ void __launch_bounds__(BLOCK) k_bc_wave(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
                                                    am_retry next) {
@@ -163,7 +163,7 @@ __global__ void __launch_bounds__(BLOCK) k_bc_wave(am_op_log L, am_read_batch B,
         uint64_t tx[OL] = {};
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) lw[d][0] = d < (int)nd ? *(const uint32_t *)(L.lag + (uint64_t)d * stride + g) : 0u;
-        ib = pk_tile_lag<DMAX, OL, false>(u, pk, lr, c, lw, tx, g, off0, off1, ap, esc);
+        ib = pk_tile<DMAX, OL, false>(u, pk, lag_ent(c, lw, lr.lb), tx, g, off0, off1, ap, esc);
       } else {
         uint32_t x[OL][DMAX];
         uint64_t tx[OL];
@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(BLOCK) k_bc_wave(am_op_log L, am_read_batch B,
 #pragma unroll
           for (int k = 0; k < OL; ++k) x[k][d] = q[k];
         }
-        ib = pk_tile<DMAX, OL, false>(u, pk, x, tx, g, off0, off1, ap, esc);
+        ib = pk_tile<DMAX, OL, false>(u, pk, pk_ent(x), tx, g, off0, off1, ap, esc);
       }
 #pragma unroll
       for (int k = 0; k < OL; ++k)
@@ -193,7 +193,7 @@ __global__ void __launch_bounds__(BLOCK) k_bc_wave(am_op_log L, am_read_batch B,
     }
     if (!GENERAL) a.reset();
     if constexpr (!GENERAL && DMAX <= 8) {
-      if (__ballot(esc)) {  // rare: ops outside the packed view, from the full columns
+      if (__ballot(esc)) {  // rare: ops outside the packed view, through the escape reader
         for (uint64_t p = off0 + lane; p < off1; p += WAVE) {
           if (L.pk_vc[p] != AM_PK_ESC) continue;
           uint64_t sv[DMAX], ct;
@@ -205,43 +205,19 @@ __global__ void __launch_bounds__(BLOCK) k_bc_wave(am_op_log L, am_read_batch B,
       }
     } else if constexpr (!GENERAL) {
       if (__ballot(esc)) {
-        // D > 8: the same, eval_op<DMAX, false> one DC at a time (the clock entry from lane d)
-        // and the included ops' maxima into LDS, so the pass holds no D-wide arrays (it would
-        // set the kernel's register peak)
+        // D > 8: the same one DC at a time (esc_eval_lean: the clock entry from lane d, the
+        // included ops' maxima into LDS), so the pass holds no D-wide arrays (it would set the
+        // kernel's register peak)
         uint64_t vS = 0;
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) vS = (uint32_t)d == lane ? u.S[d] : vS;
         const uint32_t *escv = lr.on ? L.lag_ct : L.pk_vc;  // the view the loop streamed
         for (uint64_t p = off0 + lane; p < off1; p += WAVE) {
           if (escv[p] != AM_PK_ESC) continue;
-          // a lag-only escape (the packed view holds the op): its packed entries, K + entry;
-          // else its escape row, or the columns
-          const bool pkd = L.pk_vc[p] != AM_PK_ESC;
-          const uint64_t *w = pkd ? nullptr : esc_row(L, stride, p);
-          const uint32_t meta = w ? (uint32_t)w[1] : L.op_meta[p], dc = meta & 31u;
-          auto xd = [&](uint32_t d) -> uint64_t {
-            if (pkd) return pk.K + L.pk_vc[(uint64_t)d * stride + p];
-            if (d == dc) return w ? w[0] : L.commit_time[p];
-            return w ? w[2 + d] : L.snap_vc[(uint64_t)d * stride + p];
-          };
-          bool incl = true;
-          for (uint32_t d = 0; d < nd; ++d) {
-            if (!((u.spres >> d) & 1u)) {  // logger:error("Could not find DC in SS"); excluded
-              incl = false;
-              a.flags |= AM_FLAG_MISSING_DC_LOGGED;
-              continue;
-            }
-            incl &= xd(d) <= lane_u64(vS, d);
-          }
-          if (!incl) {
-            a.min_excl = p < a.min_excl ? p : a.min_excl;
-            continue;
-          }
-          for (uint32_t d = 0; d < nd; ++d) atomicMax((unsigned long long *)&s.emx[d], (unsigned long long)xd(d));
-          a.pres |= u.allmask;
-          a.count += 1;
-          if (meta & AM_META_BAD) a.flags |= FLAG_BAD;
-          apply(meta, (int64_t)L.p0[p], L.p1[p]);
+          // (pk.K also where the loop streamed pk_vc: the op is escaped from it, so never rebuilt)
+          const EscOp e = esc_open(L, stride, p, pk.K);
+          if (!esc_eval_lean(e, u, nd, vS, (unsigned long long *)s.emx, a)) continue;
+          apply(e.meta, (int64_t)L.p0[p], L.p1[p]);
         }
         wave_sync();
 #pragma unroll

@@ -505,8 +505,8 @@ __global__ void __launch_bounds__(BLOCK) k_big_chunk(am_op_log L, am_read_batch 
 
 // ---- LEAN evaluation (packed view, the batch clock: no bases / TxIds / op presence): the clock
 //      is read once per kernel and the chunk loops test the packed entries only; an escaped op
-//      is evaluated from the full columns one DC at a time (lane d's vS holds the clock's entry
-//      d) with its LastOpCt maxima into an LDS array -- the loops hold no D-wide u64 arrays
+//      is evaluated through the escape reader one DC at a time (am_wave.h esc_eval_lean: lane
+//      d's vS holds the clock's entry d) with its LastOpCt maxima into an LDS array -- the loops hold no D-wide u64 arrays
 //      (D = 16: k_big_gincl 227 -> 155 VGPRs).  eval_op<DMAX, false> semantics. ----
 template <int DMAX>
 __device__ __forceinline__ void lean_clock(const am_read_batch &B, uint32_t nd, uint32_t lane, ReadU<DMAX> &u,
@@ -541,7 +541,7 @@ __device__ __forceinline__ uint32_t lean_incl4(const am_op_log &L, uint32_t nd, 
       const uint2 v = d < (int)nd ? *(const uint2 *)(L.lag + (uint64_t)d * stride + g) : uint2{0, 0};
       lw[d][0] = v.x, lw[d][1] = v.y;
     }
-    ib = pk_tile_lag<DMAX, 4, false>(u, pk, lr, c, lw, tx, g, lo, hi, ap, esc);
+    ib = pk_tile<DMAX, 4, false>(u, pk, lag_ent(c, lw, lr.lb), tx, g, lo, hi, ap, esc);
   } else {
     uint32_t xs[4][DMAX];
 #pragma unroll
@@ -550,7 +550,7 @@ __device__ __forceinline__ uint32_t lean_incl4(const am_op_log &L, uint32_t nd, 
       if (d < (int)nd) q = *(const u32x4 *)(L.pk_vc + (uint64_t)d * stride + g);
       xs[0][d] = q.x, xs[1][d] = q.y, xs[2][d] = q.z, xs[3][d] = q.w;
     }
-    ib = pk_tile<DMAX, 4, false>(u, pk, xs, tx, g, lo, hi, ap, esc);
+    ib = pk_tile<DMAX, 4, false>(u, pk, pk_ent(xs), tx, g, lo, hi, ap, esc);
   }
   if (!esc) return ib;
   const uint32_t *escv = lr.on ? L.lag_ct : L.pk_vc;
@@ -558,34 +558,8 @@ __device__ __forceinline__ uint32_t lean_incl4(const am_op_log &L, uint32_t nd, 
   for (int k = 0; k < 4; ++k) {  // rare
     const uint64_t p = g + k;
     if (p < lo || p >= hi || escv[p] != AM_PK_ESC) continue;
-    // a lag-only escape (the packed view holds the op): its packed entries, K + entry; else
-    // its escape row, or the columns
-    const bool pkd = lr.on && L.pk_vc[p] != AM_PK_ESC;
-    const uint64_t *w = pkd ? nullptr : esc_row(L, stride, p);
-    const uint32_t meta = w ? (uint32_t)w[1] : L.op_meta[p], dc = meta & 31u;
-    auto xd = [&](uint32_t d) -> uint64_t {
-      if (pkd) return pk.K + L.pk_vc[(uint64_t)d * stride + p];
-      if (d == dc) return w ? w[0] : L.commit_time[p];
-      return w ? w[2 + d] : L.snap_vc[(uint64_t)d * stride + p];
-    };
-    bool in = true;
-    for (uint32_t d = 0; d < nd; ++d) {
-      if (!((u.spres >> d) & 1u)) {  // logger:error("Could not find DC in SS"); excluded
-        in = false;
-        a.flags |= AM_FLAG_MISSING_DC_LOGGED;
-        continue;
-      }
-      in &= xd(d) <= lane_u64(vS, d);
-    }
-    if (!in) {
-      a.min_excl = p < a.min_excl ? p : a.min_excl;
-      continue;
-    }
-    for (uint32_t d = 0; d < nd; ++d) atomicMax(&emx[d], (unsigned long long)xd(d));
-    a.pres |= u.allmask;
-    a.count += 1;
-    if (meta & AM_META_BAD) a.flags |= FLAG_BAD;
-    ib |= 1u << k;
+    // (pk.K also where the loop streamed pk_vc: the op is escaped from it, so never rebuilt)
+    if (esc_eval_lean(esc_open(L, stride, p, pk.K), u, nd, vS, emx, a)) ib |= 1u << k;
   }
   return ib;
 }

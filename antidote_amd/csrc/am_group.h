@@ -206,10 +206,10 @@ __device__ __forceinline__ void ld_n32(const uint32_t *p, uint32_t *o) {
 }
 
 // the OPL ops [g, g + OPL) of a read's [off0, off1): inclusion bits (is_op_in_snapshot/7).
-// Packed view: u32 entries relative to the key's time base (am_wave.h pk_eval), partials in
-// ap; an escaped op (pk_vc[0] == AM_PK_ESC) is not evaluated here: esc is set and the
-// caller's escape pass (esc_pass) evaluates it from the full columns, off the hot loop.  With
-// the lag view (lr.on) the same from 4 + 2 D bytes per op (escapes: lag_ct == AM_PK_ESC).
+// Packed view: u32 entries relative to the key's time base (am_wave.h pk_tile), partials in
+// ap; an op the streamed view does not hold (pk_vc[0] == AM_PK_ESC; with the lag view, lr.on,
+// 4 + 2 D bytes per op: lag_ct == AM_PK_ESC) only sets esc: the caller's escape pass (esc_pass)
+// evaluates it off the hot loop by the two-level rule of am_wave.h esc_load.
 // Full view: eval_op on the u64 columns, partials in a.
 template <int DMAX, int OPL, bool GENERAL, bool PACKED>
 __device__ __forceinline__ uint32_t eval_tile(const am_op_log &L, uint32_t nd, const ReadU<DMAX> &u,
@@ -234,7 +234,7 @@ __device__ __forceinline__ uint32_t eval_tile(const am_op_log &L, uint32_t nd, c
         lw[d][0] = d < (int)nd ? (uint32_t)*lp : 0u;
       }
     }
-    ib = pk_tile_lag<DMAX, OPL, GENERAL>(u, pk, lr, c, lw, tx, g, off0, off1, ap, esc);
+    ib = pk_tile<DMAX, OPL, GENERAL>(u, pk, lag_ent(c, lw, lr.lb), tx, g, off0, off1, ap, esc);
   } else if (PACKED) {
     uint32_t x[OPL][DMAX];
 #pragma unroll
@@ -244,7 +244,7 @@ __device__ __forceinline__ uint32_t eval_tile(const am_op_log &L, uint32_t nd, c
 #pragma unroll
       for (int k = 0; k < OPL; ++k) x[k][d] = q[k];
     }
-    ib = pk_tile<DMAX, OPL, GENERAL>(u, pk, x, tx, g, off0, off1, ap, esc);
+    ib = pk_tile<DMAX, OPL, GENERAL>(u, pk, pk_ent(x), tx, g, off0, off1, ap, esc);
   } else {
     uint64_t ct[OPL], sv[OPL][DMAX];
     uint32_t sp[OPL];
@@ -273,9 +273,9 @@ __device__ __forceinline__ uint32_t eval_tile(const am_op_log &L, uint32_t nd, c
   return ib;
 }
 
-// the escaped ops of ops [off0, off1) handled by this lane (p = off0 + lane0, step nl), from
-// their packed entries (a lag-only escape; K: the key's time base) or the full columns
-// (esc_load); included ones are OR-ed into the LDS bitmap (bit = p - t0)
+// the escaped ops (escv[p] == AM_PK_ESC, escv the view the read streamed) of ops [off0, off1)
+// handled by this lane (p = off0 + lane0, step nl), through esc_load (K: the key's time base when
+// the read streamed the lag view, else NONE); included ones are OR-ed into the LDS bitmap (p - t0)
 template <int DMAX, bool GENERAL>
 __device__ __forceinline__ void esc_pass(const am_op_log &L, uint32_t nd, const ReadU<DMAX> &u, uint64_t off0,
                                       uint64_t off1, uint64_t t0, uint64_t stride, uint32_t lane0, uint32_t nl,
@@ -468,7 +468,7 @@ __global__ void __launch_bounds__(WBLOCK, 4) k_grp_wg(am_op_log L, am_read_batch
       if (lane % LPW == 0) s.incl[(uint32_t)((t - t0) / 32) + tid / LPW] = word;
     }
     const bool full = !PACKED || __syncthreads_or(esc);
-    if (PACKED && full)  // rare: ops outside the packed view, from the full columns
+    if (PACKED && full)  // rare: ops outside the packed view, through the escape reader
       esc_pass<DMAX, GENERAL>(L, nd, u, m.off0, m.off1, t0, stride, tid, WBLOCK, s.incl, a,
                               lr.on ? L.lag_ct : L.pk_vc, lr.on ? pk.K : NONE);
     {  // wave partials of the scalar outputs (VGPR reductions: the scalar file is full)
@@ -1076,7 +1076,7 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_op_log L, 
       }
       wave_sync();
       const bool full = !BM && (!PACKED || __ballot(esc));
-      if (PACKED && full) {  // rare: ops outside the packed view, from the full columns
+      if (PACKED && full) {  // rare: ops outside the packed view, through the escape reader
         esc_pass<DMAX, GENERAL>(L, nd, u, off0, off1, t0, stride, lane, WAVE, s.incl, a, lr.on ? L.lag_ct : L.pk_vc,
                                 lr.on ? pk.K : NONE);
         wave_sync();
@@ -1239,58 +1239,27 @@ struct ISmem {
   uint32_t flags[IWB];
 };
 
-// ops [g, g + OPL) of the lane (OPL consecutive slots, g OPL-aligned), packed view: inclusion
-// bits (is_op_in_snapshot/7 against the batch clock: every entry X[d] - K <= S[d] - K) and the
-// partials.  RANGE: the tile may hold slots outside [off0, off1); escaped ops (x[0] == ESC)
-// are left to the caller (esc bit k).
-template <int DMAX, int OPL, bool RANGE>
-__device__ __forceinline__ uint32_t incl_tile(const uint32_t (&x)[OPL][DMAX], const PkRead<DMAX> &pk, uint64_t g,
-                                              uint64_t off0, uint64_t off1, uint32_t (&mx)[DMAX], uint32_t &esc,
-                                              uint32_t &cand) {
+// ops [g, g + OPL) of the lane (OPL consecutive slots, g OPL-aligned), their entries x those of
+// the packed view (pk_ent) or rebuilt from the lag view where they are used (lag_ent, am_wave.h):
+// inclusion bits (is_op_in_snapshot/7 against the batch clock: every entry X[d] - K <= S[d] - K)
+// and the partials.  RANGE: the tile may hold slots outside [off0, off1); escaped ops
+// (x.esc(k) == AM_PK_ESC) are left to the caller (esc bit k).
+template <int DMAX, int OPL, bool RANGE, class Ent>
+__device__ __forceinline__ uint32_t incl_tile(const Ent &x, const PkRead<DMAX> &pk, uint64_t g, uint64_t off0,
+                                              uint64_t off1, uint32_t (&mx)[DMAX], uint32_t &esc, uint32_t &cand) {
   uint32_t ib = 0;
 #pragma unroll
   for (int k = 0; k < OPL; ++k) {
-    const bool e = x[k][0] == AM_PK_ESC;
+    const bool e = x.esc(k) == AM_PK_ESC;
     const bool inr = !RANGE || (g + k >= off0 && g + k < off1);
     bool in = inr && !e;
 #pragma unroll
-    for (int d = 0; d < DMAX; ++d) in = in && x[k][d] <= pk.thr[d];
+    for (int d = 0; d < DMAX; ++d) in = in && x(k, d) <= pk.thr[d];
     esc |= (uint32_t)(inr && e) << k;
     cand |= (uint32_t)(inr && !e) << k;
     if (in) {
 #pragma unroll
-      for (int d = 0; d < DMAX; ++d) mx[d] = max(mx[d], x[k][d]);
-    }
-    ib |= (uint32_t)in << k;
-  }
-  return ib;
-}
-
-// incl_tile over the lag view: commit entries c (AM_PK_ESC: escaped), four u16 lags per DC in
-// lv, the key's lag bases lb; X[d] - K = c - (lb[d] + lag) is rebuilt where it is used (the lags
-// stay packed two per register: the rebuilt entries would hold 4 * DMAX registers)
-template <int DMAX, bool RANGE>
-__device__ __forceinline__ uint32_t incl_tile_lag(const uint32_t (&c)[4], const uint2 (&lv)[DMAX],
-                                                  const uint32_t (&lb)[DMAX], const PkRead<DMAX> &pk, uint64_t g,
-                                                  uint64_t off0, uint64_t off1, uint32_t (&mx)[DMAX], uint32_t &esc,
-                                                  uint32_t &cand) {
-  auto xd = [&](int k, int d) -> uint32_t {
-    const uint32_t w = k < 2 ? lv[d].x : lv[d].y;
-    return c[k] - (lb[d] + ((k & 1) ? w >> 16 : w & 0xFFFFu));
-  };
-  uint32_t ib = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool e = c[k] == AM_PK_ESC;
-    const bool inr = !RANGE || (g + k >= off0 && g + k < off1);
-    bool in = inr && !e;
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) in = in && xd(k, d) <= pk.thr[d];
-    esc |= (uint32_t)(inr && e) << k;
-    cand |= (uint32_t)(inr && !e) << k;
-    if (in) {
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) mx[d] = max(mx[d], xd(k, d));
+      for (int d = 0; d < DMAX; ++d) mx[d] = max(mx[d], x(k, d));
     }
     ib |= (uint32_t)in << k;
   }
@@ -1406,25 +1375,27 @@ __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, 
         // software-pipelined: tile t + 1's loads are issued before tile t is evaluated, into the
         // other of two register sets (no copies between them: a copy would wait for the loads)
         uint32_t cA[OPL], cB[OPL];
-        uint2 lA[DMAX], lB[DMAX];
-        auto load = [&](uint64_t t, uint32_t (&c)[OPL], uint2 (&lv)[DMAX]) {
+        uint32_t lA[DMAX][2], lB[DMAX][2];
+        auto load = [&](uint64_t t, uint32_t (&c)[OPL], uint32_t (&lw)[DMAX][2]) {
           const uint64_t g = t + (uint64_t)lane * OPL;
 #pragma unroll
           for (int k = 0; k < OPL; ++k) c[k] = 0;
           if (g < off1) ld_n32<OPL>(L.lag_ct + g, c);
 #pragma unroll
           for (int d = 0; d < DMAX; ++d) {
-            lv[d] = uint2{0, 0};
-            if (d < (int)nd && g < off1) lv[d] = *(const uint2 *)(L.lag + (uint64_t)d * stride + g);
+            uint2 v = {0, 0};
+            if (d < (int)nd && g < off1) v = *(const uint2 *)(L.lag + (uint64_t)d * stride + g);
+            lw[d][0] = v.x, lw[d][1] = v.y;
           }
         };
-        auto eval = [&](uint64_t t, const uint32_t (&c)[OPL], const uint2 (&lv)[DMAX]) {
+        auto eval = [&](uint64_t t, const uint32_t (&c)[OPL], const uint32_t (&lw)[DMAX][2]) {
           const uint64_t g = t + (uint64_t)lane * OPL;
           uint32_t esc = 0, cand = 0;
           const bool whole = t >= off0 && t + TILE <= off1;
           // (pad DCs d >= nd: c - lb[d] with lb = 0 lies under the always-passing pad threshold)
-          const uint32_t ib = whole ? incl_tile_lag<DMAX, false>(c, lv, lb, pk, g, off0, off1, mx, esc, cand)
-                                    : incl_tile_lag<DMAX, true>(c, lv, lb, pk, g, off0, off1, mx, esc, cand);
+          const auto x = lag_ent(c, lw, lb);
+          const uint32_t ib = whole ? incl_tile<DMAX, OPL, false>(x, pk, g, off0, off1, mx, esc, cand)
+                                    : incl_tile<DMAX, OPL, true>(x, pk, g, off0, off1, mx, esc, cand);
           tile_out(t, g, ib, esc, cand);
         };
         load(t0, cA, lA);
@@ -1449,8 +1420,8 @@ __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, 
 #pragma unroll
             for (int k = 0; k < OPL; ++k) x[k][d] = q[k];
           }
-          const uint32_t ib = whole ? incl_tile<DMAX, OPL, false>(x, pk, g, off0, off1, mx, esc, cand)
-                                    : incl_tile<DMAX, OPL, true>(x, pk, g, off0, off1, mx, esc, cand);
+          const uint32_t ib = whole ? incl_tile<DMAX, OPL, false>(pk_ent(x), pk, g, off0, off1, mx, esc, cand)
+                                    : incl_tile<DMAX, OPL, true>(pk_ent(x), pk, g, off0, off1, mx, esc, cand);
           tile_out(t, g, ib, esc, cand);
         }
       }
@@ -1479,7 +1450,7 @@ __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, 
       uint64_t mxl = (lane < nd && count_p) ? pk.K + mxd : 0;
       uint32_t count = count_p, flags = cands ? pk.miss : 0u, pres = count_p ? u.allmask : 0u;
       uint64_t min_excl = minex == 0xFFFFFFFFu ? NONE : t0 + minex;
-      if (escs) {  // rare: ops outside the packed view, from the full columns (bits ORed in)
+      if (escs) {  // rare: ops outside the streamed view, through the escape reader (bits ORed in)
         Acc<DMAX> a;
         a.reset();
         __builtin_amdgcn_s_waitcnt(0);
@@ -1780,11 +1751,11 @@ __global__ void __launch_bounds__(BLOCK) k_grp_row(am_op_log L, am_read_batch B,
       ap.reset();
       bool esc = false;
       uint64_t incl = 0;
-      // one op from the full columns (full view, or an op outside the packed view)
+      // one op at full width (full view, or an op outside the packed view: the escape reader)
       auto eval_full = [&](uint64_t p) -> bool {
         uint64_t svf[DMAX], ct;
         uint32_t meta;
-        esc_load<DMAX>(L, nd, stride, p, NONE, svf, ct, meta);  // (the columns when the op has no row)
+        esc_load<DMAX>(L, nd, stride, p, NONE, svf, ct, meta);
         const uint32_t sp = (GENERAL && L.snap_pres) ? L.snap_pres[p] : u.allmask;
         const bool txm = GENERAL && u.has_txid && L.op_txid[p] == u.txid;
         return eval_op<DMAX, GENERAL>(u, meta, ct, svf, sp, txm, p, a) && !(meta & AM_META_BAD);
@@ -1807,7 +1778,7 @@ __global__ void __launch_bounds__(BLOCK) k_grp_row(am_op_log L, am_read_batch B,
         }
         incl |= ((__ballot(in) >> (row * RG)) & 0xFFFFull) << (RG * k);
       }
-      if (PACKED && __ballot(esc)) {  // rare: ops outside the packed view, from the full columns
+      if (PACKED && __ballot(esc)) {  // rare: ops outside the packed view, through the escape reader
 #pragma unroll
         for (uint32_t k = 0; k < ROW_OPS / RG; ++k) {
           const uint64_t p = m.off0 + sl + RG * k;

@@ -275,7 +275,7 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_g(am_op_log L, am_read_batch B,
       if (u.has_txid) ld_n64<OPL>(L.op_txid + g, cur.tx);
       if (scal) ld_n64<OPL>(L.p0 + g, cur.v0);
       if (t == AM_LWW) ld_n64<OPL>(L.p1 + g, cur.v1);
-      const uint32_t ib = pk_tile<DMAX, OPL, true>(u, pk, cur.x, cur.tx, g, off0, off1, ap, esc);
+      const uint32_t ib = pk_tile<DMAX, OPL, true>(u, pk, pk_ent(cur.x), cur.tx, g, off0, off1, ap, esc);
       incl |= (uint64_t)ib << (g - t0);
       if (scal) {
 #pragma unroll
@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_g(am_op_log L, am_read_batch B,
           }
       }
     }
-    if (esc) {  // rare: ops outside the packed view, from the full columns
+    if (esc) {  // rare: ops outside the packed view, through the escape reader
       for (uint64_t p = off0; p < off1; ++p) {
         if (L.pk_vc[p] != AM_PK_ESC) continue;
         uint64_t sv[DMAX], ct;
@@ -825,7 +825,7 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_q(am_op_log L, am_read_batch B,
         u32x4 e0 = {0, 0, 0, 0}, e1 = e0, e2 = e0, e3 = e0;
         if (scal) e0 = *(const u32x4 *)(L.p0 + g), e1 = *(const u32x4 *)(L.p0 + g + 2);
         if (t == AM_LWW) e2 = *(const u32x4 *)(L.p1 + g), e3 = *(const u32x4 *)(L.p1 + g + 2);
-        const uint32_t ib = pk_tile<DMAX, 4, false>(u, pk, x, tx0, g, off0, off1, ap, esc);
+        const uint32_t ib = pk_tile<DMAX, 4, false>(u, pk, pk_ent(x), tx0, g, off0, off1, ap, esc);
         incl |= (uint64_t)ib << (g - a0);
         if (t == AM_PN) q_pn(ib, e0, e1, pv);
         if (t == AM_LWW) q_lww(ib, e0, e1, e2, e3, lv);
@@ -833,7 +833,7 @@ __global__ void __launch_bounds__(LBLOCK) k_lane_q(am_op_log L, am_read_batch B,
       for (uint64_t q = rk0 & ~3ull; setr && q < rk1; q += 4)
         rec_bits(*(const u32x4 *)(L.rec_g + q), q, rk0, rk1, incl, (uint32_t)(off0 - a0), born, killed);
     }
-    if (esc) {  // rare: ops outside the packed view, from the full columns
+    if (esc) {  // rare: ops outside the streamed view, through the escape reader
       uint64_t ek = 0;  // included set ops among them: the records are redone with them
       auto esc_op = [&](uint64_t p) {
         uint64_t sv[DMAX], ct;

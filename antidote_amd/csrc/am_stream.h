@@ -19,7 +19,9 @@
 //
 // Packed view (am_pack.hip): the tile streams the op's commit vector as u32 entries relative
 // to the key's time base (4*D + payload bytes per op instead of 9 + 8*D + payload) and the
-// inclusion test runs on u32 (am_wave.h pk_eval); escaped ops are read from the full columns.
+// inclusion test runs on u32 (am_wave.h pk_eval).  This kernel streams no lag view, so its only
+// escapes are ops outside the packed view: it reads them from the full columns, not through
+// esc_load (the escape row's lookup costs it a wave per SIMD, see the tile loop).
 //
 // Per-op semantics: am_wave.h eval_op (is_op_in_snapshot/7, belongs_to_snapshot_op/3).
 // Per-read outputs: materialize/4's {ok, Value, NewLastOp, LastOpCt, IsNewSS, Count}.

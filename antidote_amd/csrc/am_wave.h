@@ -324,11 +324,33 @@ __device__ __forceinline__ const uint64_t *esc_row(const am_op_log &L, uint64_t 
   const uint32_t ri = L.pk_vc[stride + p];
   return ri ? L.esc_rows + (uint64_t)(ri - 1) * (2 + L.n_dc) : nullptr;
 }
-// commit time, meta byte and snapshot entries of op p, escaped from the view its read streamed.
-// Two levels: an op the packed view holds (a lag-only escape: lag_ct[p] == AM_PK_ESC but
-// pk_vc[p] is an entry) is rebuilt from its nd u32 packed entries, X[d] = K + entry, K the
-// key's time base (K == NONE: the caller has none -- a full-view read); an op escaped from the
-// packed view reads its escape row, or the op columns.
+// The escape reader: an op escaped from the view its read streamed, one entry at a time (the
+// D-wide form is esc_load, below).  esc_open decides once where the op comes from, by the
+// two-level rule: an op the packed view holds (a lag-only escape: lag_ct[p] == AM_PK_ESC but
+// pk_vc[p] is an entry) is rebuilt from its u32 packed entries, X[d] = K + entry, K the key's
+// time base (K == NONE: the caller has none -- its read did not stream the lag view); an op
+// escaped from the packed view too reads its escape row, or the op columns.
+struct EscOp {
+  const am_op_log &L;
+  uint64_t stride, p, K;
+  const uint64_t *w;  // the escape row (null: the columns)
+  bool pkd;           // the packed entries
+  uint32_t meta;
+  // entry d < n_dc of the op's commit vector X (the commit time at the op's own DC)
+  __device__ __forceinline__ uint64_t x(uint32_t d) const {
+    if (pkd) return K + L.pk_vc[(uint64_t)d * stride + p];
+    if (d == (meta & 31u)) return w ? w[0] : L.commit_time[p];
+    return w ? w[2 + d] : L.snap_vc[(uint64_t)d * stride + p];
+  }
+};
+__device__ __forceinline__ EscOp esc_open(const am_op_log &L, uint64_t stride, uint64_t p, uint64_t K) {
+  const bool pkd = K != NONE && L.pk_vc && L.pk_vc[p] != AM_PK_ESC;
+  const uint64_t *w = pkd ? nullptr : esc_row(L, stride, p);
+  return EscOp{L, stride, p, K, w, pkd, w ? (uint32_t)w[1] : (uint32_t)L.op_meta[p]};
+}
+// The D-wide form eval_op takes: snapshot entries sv and the commit time apart (eval_op puts it
+// in the own-DC slot itself).  Deliberately not written over EscOp: that form changes the
+// register allocation of the kernels this is inlined into ("Escape reader").
 template <int DMAX>
 __device__ __forceinline__ void esc_load(const am_op_log &L, uint32_t nd, uint64_t stride, uint64_t p, uint64_t K,
                                          uint64_t (&sv)[DMAX], uint64_t &ct, uint32_t &meta) {
@@ -354,7 +376,34 @@ __device__ __forceinline__ void esc_load(const am_op_log &L, uint32_t nd, uint64
   for (int d = 0; d < DMAX; ++d) sv[d] = d < (int)nd ? L.snap_vc[(uint64_t)d * stride + p] : 0;
 }
 
-// x[0] == AM_PK_ESC ops are the caller's (full columns)
+// eval_op<DMAX, false> of an escaped op one DC at a time (the batch clock: no base, TxId or op
+// presence): lane d's vS holds the clock entry S[d], and an included op's LastOpCt maxima go to
+// emx[d] (LDS) by atomicMax -- no D-wide u64 array, which would set the register peak of the
+// kernels that call this.  Count / pres / flags / min_excl in a.  Returns "included".
+template <int DMAX>
+__device__ __forceinline__ bool esc_eval_lean(const EscOp &e, const ReadU<DMAX> &u, uint32_t nd, uint64_t vS,
+                                              unsigned long long *emx, Acc<DMAX> &a) {
+  bool in = true;
+  for (uint32_t d = 0; d < nd; ++d) {
+    if (!((u.spres >> d) & 1u)) {  // logger:error("Could not find DC in SS"); excluded
+      in = false;
+      a.flags |= AM_FLAG_MISSING_DC_LOGGED;
+      continue;
+    }
+    in &= e.x(d) <= lane_u64(vS, d);
+  }
+  if (!in) {
+    a.min_excl = e.p < a.min_excl ? e.p : a.min_excl;
+    return false;
+  }
+  for (uint32_t d = 0; d < nd; ++d) atomicMax(&emx[d], (unsigned long long)e.x(d));
+  a.pres |= u.allmask;
+  a.count += 1;
+  if (e.meta & AM_META_BAD) a.flags |= FLAG_BAD;
+  return true;
+}
+
+// x[0] == AM_PK_ESC ops are the caller's (esc_load)
 template <int DMAX, bool GENERAL>
 __device__ __forceinline__ bool pk_eval(const PkRead<DMAX> &t, const ReadU<DMAX> &u, const uint32_t (&x)[DMAX],
                                         bool txmatch, uint64_t pos, AccP<DMAX> &a) {
@@ -394,49 +443,6 @@ __device__ __forceinline__ void pk_fold(const AccP<DMAX> &p, uint64_t K, uint32_
   a.min_excl = umin64(a.min_excl, p.min_excl);
 }
 
-// the OPL packed-view ops [g, g + OPL) of a read's [off0, off1), entries x already loaded:
-// inclusion bits (is_op_in_snapshot/7), partials in ap.  Branch-free: x - thr saturates to 0
-// iff x <= thr, so one OR per op tests every DC; LastOpCt takes the included ops' entries
-// through max chains.  An escaped op (x[k][0] == AM_PK_ESC) only sets esc.
-template <int DMAX, int OPL, bool GENERAL>
-__device__ __forceinline__ uint32_t pk_tile(const ReadU<DMAX> &u, const PkRead<DMAX> &pk, const uint32_t (&x)[OPL][DMAX],
-                                            const uint64_t (&tx)[OPL], uint64_t g, uint64_t off0, uint64_t off1,
-                                            AccP<DMAX> &ap, bool &esc) {
-  uint32_t ib = 0, ev = 0;  // ev: evaluated (in range, in the packed view, a candidate)
-#pragma unroll
-  for (int k = 0; k < OPL; ++k) {
-    const uint64_t p = g + k;
-    const bool inr = p >= off0 && p < off1;
-    const bool e = x[k][0] == AM_PK_ESC;
-    esc |= inr && e;
-    uint32_t over = 0;
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) over |= __builtin_elementwise_sub_sat(x[k][d], pk.thr[d]);
-    bool cand = inr && !e;
-    if (GENERAL) {  // belongs_to_snapshot_op: not vectorclock:le(X, base)
-      uint32_t cov = 0;
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) cov |= __builtin_elementwise_sub_sat(x[k][d], pk.cthr[d]);
-      const bool le = !pk.cnever && cov == 0;
-      cand = cand && (u.base_ignore || (u.has_txid && tx[k] == u.txid) || !le);
-    }
-    ib |= (uint32_t)(cand && !pk.never && over == 0) << k;
-    ev |= (uint32_t)cand << k;
-  }
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) {
-    uint32_t m = ap.mx[d];
-#pragma unroll
-    for (int k = 0; k < OPL; ++k) m = max(m, ((ib >> k) & 1u) ? x[k][d] : 0u);
-    ap.mx[d] = m;
-  }
-  ap.count += (uint32_t)__popc(ib);
-  const uint32_t ex = ev & ~ib;
-  if (ex) ap.min_excl = umin64(ap.min_excl, g + (uint64_t)__builtin_ctz(ex));
-  if (ev) ap.flags |= pk.miss;
-  return ib;
-}
-
 // a read over the lag view (am_op_log.lag_ct / lag / key_lag): its key's lag bases
 template <int DMAX>
 struct LagRead {
@@ -452,33 +458,64 @@ __device__ __forceinline__ void lag_setup(const am_op_log &L, uint32_t nd, uint6
   for (int d = 0; d < DMAX; ++d) lr.lb[d] = on && d < (int)nd ? uniform_u32((uint32_t)L.key_lag[key * nd + d]) : 0u;
 }
 
-// pk_tile (am_wave.h) over the lag view: the OPL ops' commit entries c (AM_PK_ESC: escaped, or a
-// lag beyond 16 bits) and their u16 lags lw (two per word), the entries X[d] - K = c - (lb[d] +
-// lag) rebuilt where the compares and the max use them
-template <int DMAX, int OPL, bool GENERAL>
-__device__ __forceinline__ uint32_t pk_tile_lag(const ReadU<DMAX> &u, const PkRead<DMAX> &pk, const LagRead<DMAX> &lr,
-                                                const uint32_t (&c)[OPL], const uint32_t (&lw)[DMAX][(OPL + 1) / 2],
-                                                const uint64_t (&tx)[OPL], uint64_t g, uint64_t off0, uint64_t off1,
-                                                AccP<DMAX> &ap, bool &esc) {
-  auto xd = [&](int k, int d) -> uint32_t {
+// ---- the entries of a tile of OPL consecutive ops, as the tile tests (pk_tile here, incl_tile
+// in am_group.h) read them: x(k, d) = X[d] - K of op k, x.esc(k) = the word of op k that holds
+// AM_PK_ESC when the view does not hold the op.  Both index loaded registers only.
+// The packed view: the entries themselves.
+template <int DMAX, int OPL>
+struct PkEnt {
+  const uint32_t (&e)[OPL][DMAX];
+  __device__ __forceinline__ uint32_t operator()(int k, int d) const { return e[k][d]; }
+  __device__ __forceinline__ uint32_t esc(int k) const { return e[k][0]; }
+};
+template <int DMAX, int OPL>
+__device__ __forceinline__ PkEnt<DMAX, OPL> pk_ent(const uint32_t (&e)[OPL][DMAX]) {
+  return {e};
+}
+// The lag view: the ops' commit entries c (AM_PK_ESC: escaped, or a lag beyond 16 bits), their
+// u16 lags lw (two per word) and the key's lag bases lb; X[d] - K = c - (lb[d] + lag) is rebuilt
+// at each use (the lags stay packed two per register: rebuilt entries kept in an array would
+// hold OPL * DMAX registers)
+template <int DMAX, int OPL>
+struct LagEnt {
+  const uint32_t (&c)[OPL];
+  const uint32_t (&lw)[DMAX][(OPL + 1) / 2];
+  const uint32_t (&lb)[DMAX];
+  __device__ __forceinline__ uint32_t operator()(int k, int d) const {
     const uint32_t w = lw[d][k / 2];
-    return c[k] - (lr.lb[d] + ((k & 1) ? w >> 16 : w & 0xFFFFu));
-  };
-  uint32_t ib = 0, ev = 0;
+    return c[k] - (lb[d] + ((k & 1) ? w >> 16 : w & 0xFFFFu));
+  }
+  __device__ __forceinline__ uint32_t esc(int k) const { return c[k]; }
+};
+template <int DMAX, int OPL>
+__device__ __forceinline__ LagEnt<DMAX, OPL> lag_ent(const uint32_t (&c)[OPL], const uint32_t (&lw)[DMAX][(OPL + 1) / 2],
+                                                     const uint32_t (&lb)[DMAX]) {
+  return {c, lw, lb};
+}
+
+// the OPL ops [g, g + OPL) of a read's [off0, off1), entries x (pk_ent / lag_ent) already
+// loaded: inclusion bits (is_op_in_snapshot/7), partials in ap.  Branch-free: x - thr saturates
+// to 0 iff x <= thr, so one OR per op tests every DC; LastOpCt takes the included ops' entries
+// through max chains.  An escaped op (x.esc(k) == AM_PK_ESC) only sets esc.
+template <int DMAX, int OPL, bool GENERAL, class Ent>
+__device__ __forceinline__ uint32_t pk_tile(const ReadU<DMAX> &u, const PkRead<DMAX> &pk, const Ent &x,
+                                            const uint64_t (&tx)[OPL], uint64_t g, uint64_t off0, uint64_t off1,
+                                            AccP<DMAX> &ap, bool &esc) {
+  uint32_t ib = 0, ev = 0;  // ev: evaluated (in range, in the view, a candidate)
 #pragma unroll
   for (int k = 0; k < OPL; ++k) {
     const uint64_t p = g + k;
     const bool inr = p >= off0 && p < off1;
-    const bool e = c[k] == AM_PK_ESC;
+    const bool e = x.esc(k) == AM_PK_ESC;
     esc |= inr && e;
     uint32_t over = 0;
 #pragma unroll
-    for (int d = 0; d < DMAX; ++d) over |= __builtin_elementwise_sub_sat(xd(k, d), pk.thr[d]);
+    for (int d = 0; d < DMAX; ++d) over |= __builtin_elementwise_sub_sat(x(k, d), pk.thr[d]);
     bool cand = inr && !e;
     if (GENERAL) {  // belongs_to_snapshot_op: not vectorclock:le(X, base)
       uint32_t cov = 0;
 #pragma unroll
-      for (int d = 0; d < DMAX; ++d) cov |= __builtin_elementwise_sub_sat(xd(k, d), pk.cthr[d]);
+      for (int d = 0; d < DMAX; ++d) cov |= __builtin_elementwise_sub_sat(x(k, d), pk.cthr[d]);
       const bool le = !pk.cnever && cov == 0;
       cand = cand && (u.base_ignore || (u.has_txid && tx[k] == u.txid) || !le);
     }
@@ -489,7 +526,7 @@ __device__ __forceinline__ uint32_t pk_tile_lag(const ReadU<DMAX> &u, const PkRe
   for (int d = 0; d < DMAX; ++d) {
     uint32_t m = ap.mx[d];
 #pragma unroll
-    for (int k = 0; k < OPL; ++k) m = max(m, ((ib >> k) & 1u) ? xd(k, d) : 0u);
+    for (int k = 0; k < OPL; ++k) m = max(m, ((ib >> k) & 1u) ? x(k, d) : 0u);
     ap.mx[d] = m;
   }
   ap.count += (uint32_t)__popc(ib);
@@ -501,7 +538,7 @@ __device__ __forceinline__ uint32_t pk_tile_lag(const ReadU<DMAX> &u, const PkRe
 
 // Inclusion of the 4 ops [g, g + 4) of one read inside [lo, hi) (is_op_in_snapshot/7 +
 // belongs_to_snapshot_op/3, every clock general): bit k = op g + k included.  Packed view
-// (PACKED): u32 entries through pk_tile, partials in ap, escaped ops from the full columns;
+// (PACKED): u32 entries through pk_tile, partials in ap, escaped ops through esc_load;
 // full view: eval_op on the u64 columns, partials in a.  AM_META_BAD ops are included here
 // (eval_op flags them); callers skip their effects.
 template <int DMAX, bool PACKED>
@@ -523,7 +560,7 @@ __device__ __forceinline__ uint32_t incl4(const am_op_log &L, uint32_t nd, uint6
       if (d < (int)nd) q = *(const u32x4 *)(L.pk_vc + (uint64_t)d * stride + g);
       x[0][d] = q.x, x[1][d] = q.y, x[2][d] = q.z, x[3][d] = q.w;
     }
-    ib = pk_tile<DMAX, 4, true>(u, pk, x, tx, g, lo, hi, ap, esc);
+    ib = pk_tile<DMAX, 4, true>(u, pk, pk_ent(x), tx, g, lo, hi, ap, esc);
     if (!esc) return ib;
   }
 #pragma unroll

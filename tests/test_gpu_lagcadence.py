@@ -7,8 +7,9 @@ their ops are such (include/antidote_mat.h, the lag view's reader contract).
    am_pk_base) or 2^31 (escaped from the packed view too: the escape row), read at clocks swept
    across each such entry at +-1, in three regimes (tight / sparse / heavy) whose view counters
    (am_store_view_stats) must equal the counts computed here in numpy from the definition.
-2. Synthetic populations with gst_ppm (csrc/synth.h am_syn_snap_g): full parity over every key.
-3. In place: am_store_apply carries the routing decision and frees slots as escaped.
+2. Escaped ops read with a clock that lacks a DC, in every tier's escape walk.
+3. Synthetic populations with gst_ppm (csrc/synth.h am_syn_snap_g): full parity over every key.
+4. In place: am_store_apply carries the routing decision and frees slots as escaped.
 Every result is compared with the oracle (oracle/am_oracle.c)."""
 import random
 
@@ -121,17 +122,18 @@ def make_keys(rng, t, n_dc, lens, regime, n_first=None):
     return keys, sweeps
 
 
-def check_batch(mat, dlog, log, keys, t, n_dc, clock, cap=512, sel=None):
-    """One batch-clock read of the keys `sel` (every key when None) against the oracle."""
+def check_batch(mat, dlog, log, keys, t, n_dc, clock, cap=512, sel=None, pres=None):
+    """One batch-clock read of the keys `sel` (every key when None) against the oracle.  pres: the
+    mask of the DCs the clock holds (every DC when None)."""
     sel = list(range(len(keys))) if sel is None else list(sel)
     n = len(sel)
     kt = torch.tensor(sel, dtype=torch.int64, device="cuda")
-    dr = DeviceReads(n, n_dc, t, clock, set_cap=cap, keys=kt)
+    dr = DeviceReads(n, n_dc, t, clock, pres=pres, set_cap=cap, keys=kt)
     torch.cuda.synchronize()
     materialize(mat, dlog, dr)
     mat.sync()
     h = dr.host()
-    reads = [Read(k, t, {d: clock[d] for d in range(n_dc)}) for k in sel]
+    reads = [Read(k, t, {d: clock[d] for d in range(n_dc) if pres is None or (pres >> d) & 1}) for k in sel]
     ref = amo.materialize(log, HostBatch(n_dc, reads, randlog.caps_for(reads, n_dc, cap)))
     ok = [i for i in range(n) if ref.result(i)[0] == "ok"]
     vals = dr.values(np.asarray(ok, np.int64)) if ok else []
@@ -232,6 +234,46 @@ def test_gpu_lag_boundaries(mat, t, n_dc, lens, incremental, regime):
                 ref1 = amo.materialize(log, HostBatch(n_dc, r1, caps))
                 for i in range(n):
                     assert h1.result(i) == ref1.result(i), (i, len(keys[i]), clocks[i], h1.result(i), ref1.result(i))
+    finally:
+        st.close()
+
+
+# ---------------------------------------------------------------- escaped ops, a DC missing
+# lengths of CASES that reach each type's row, wave, workgroup and big tiers
+MISSING_DC = [(abi.AM_BCOUNTER, 16, [40, 300, 5000]),
+              (abi.AM_AWSET, 8, [40, 300, 1500, 9000]),
+              (abi.AM_PN, 3, [16, 64, 300])]
+
+
+@pytest.mark.parametrize("every", [False, True], ids=["sparse", "all_escaped"])
+@pytest.mark.parametrize("t,n_dc,lens", MISSING_DC)
+def test_gpu_escape_missing_dc(mat, t, n_dc, lens, every):
+    """Escaped ops read with a clock that lacks a DC ("Could not find DC in SS": the op is excluded
+    and AM_FLAG_MISSING_DC_LOGGED set).  sparse: make_keys' sparse regime, a few lag-only escapes
+    and one FAR escape per key, nothing routed.  all_escaped: every op has one remote entry FAR
+    below its commit time, so every op is outside the packed view and the escape reader alone
+    decides each read.  Every key is read at a clock past its newest op with every DC present and
+    with DC 0, DC n_dc - 1 and a middle DC absent."""
+    rng = random.Random(7400 + 10 * t + every)
+    keys, _ = make_keys(rng, t, n_dc, lens, "tight" if every else "sparse")
+    if every:
+        for ops in keys:
+            for op in ops:
+                op.snap[(op.commit_dc + 1) % n_dc] = op.commit_time - FAR
+    log = HostLog(n_dc, keys, key_types=[t] * len(keys))
+    st = mat.store(log)
+    try:
+        stats = st.view_stats()
+        assert stats == view_counts(log)[0], stats
+        if every:
+            assert stats["pk_esc_ops"] == stats["ops"] == sum(lens), stats
+        else:
+            assert stats["routed_keys"] == 0 and stats["pk_esc_ops"] > 0 and stats["lag_only_esc_ops"] > 0, stats
+        dlog = st.device_log()
+        _, hi = span(keys)
+        full = (1 << n_dc) - 1
+        for pres in [None] + [full & ~(1 << d) for d in (0, n_dc - 1, n_dc // 2)]:
+            check_batch(mat, dlog, log, keys, t, n_dc, [hi] * n_dc, pres=pres)
     finally:
         st.close()
 
