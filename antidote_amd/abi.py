@@ -60,6 +60,7 @@ class am_op_log(ctypes.Structure):
         ("key_ngrp", c_void_p), ("key_end", c_void_p), ("rec_key_end", c_void_p), ("gmask", c_void_p),
         ("zone_vc", c_void_p), ("zone_gsum", c_void_p), ("prec", c_void_p), ("esc_rows", c_void_p),
         ("lag_ct", c_void_p), ("lag", c_void_p), ("key_lag", c_void_p),
+        ("key_nspan", c_void_p), ("gspan", c_void_p), ("gsrc", c_void_p),
     ]
 
 
@@ -108,6 +109,7 @@ VIEW_STATS = ("ops", "pk_esc_ops", "lag_only_esc_ops", "routed_keys", "routed_op
 AM_VIEW_STAT_N = len(VIEW_STATS)
 AM_PK_ESC = 0xFFFFFFFF
 AM_LAG_ROUTED = -(1 << 31)  # key_lag[k][0] of a packed-routed key
+AM_NSPAN_NONE = 0xFFFFFFFF  # key_nspan[k] of a key without the group-span view
 AM_ERR_COLD_PATH = 5
 AM_SNAPSHOT_THRESHOLD = 10
 AM_SNAPCACHE_ABSENT = 0xFFFFFFFF
@@ -227,7 +229,7 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
-        if L.am_abi_version() != 13:
+        if L.am_abi_version() != 14:
             raise AmError("ABI version mismatch")
         _lib = L
     return _lib

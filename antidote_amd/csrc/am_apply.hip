@@ -225,6 +225,7 @@ __global__ void __launch_bounds__(256) k_writeback(am_op_log L, am_op_log S, con
     if (L.rec_key_off) {
       const uint64_t r0 = L.rec_key_off[k];
       uint64_t nr = 0;
+      uint32_t nsp = AM_NSPAN_NONE;  // the key's span count: S's, or none (then read through rec_g)
       if (S.rec_key_off && S.key_ngrp) {
         const uint64_t sr0 = S.rec_key_off[i];
         nr = am_rkend(S, i) - sr0;
@@ -238,6 +239,12 @@ __global__ void __launch_bounds__(256) k_writeback(am_op_log L, am_op_log S, con
             pr[2 * (r0 + r) + 1] = S.prec[2 * (sr0 + r) + 1];
           }
         }
+        if (L.key_nspan && L.gspan && L.gsrc && S.key_nspan && S.gspan && S.gsrc) {  // and its spans
+          nsp = S.key_nspan[i];
+          uint32_t *gs = const_cast<uint32_t *>(L.gspan), *gr = const_cast<uint32_t *>(L.gsrc);
+          for (uint64_t r = lane; nsp != AM_NSPAN_NONE && r < nsp; r += WAVE_SZ)
+            gs[r0 + r] = S.gspan[sr0 + r], gr[r0 + r] = S.gsrc[sr0 + r];
+        }
         uint64_t *gp = const_cast<uint64_t *>(L.grp);
         const uint32_t ngc = am_ngrp_count(ng);
         for (uint32_t g = lane; g < ngc; g += WAVE_SZ) {
@@ -248,6 +255,7 @@ __global__ void __launch_bounds__(256) k_writeback(am_op_log L, am_op_log S, con
       if (lane == 0) {
         const_cast<uint64_t *>(L.rec_key_end)[k] = r0 + nr;
         const_cast<uint32_t *>(L.key_ngrp)[k] = ng;
+        if (L.key_nspan) const_cast<uint32_t *>(L.key_nspan)[k] = nsp;
       }
     }
     if (lane == 0) {
@@ -381,6 +389,7 @@ int am_store_apply_ex(am_ctx *c, am_store *st, uint64_t m, const uint64_t *d_key
   view.key_off = V.off, view.key_end = V.end, view.key_id_base = V.idb, view.key_type = V.type, view.key_flags = V.flags;
   view.key_tbase = nullptr, view.rec_key_off = nullptr, view.rec_key_end = nullptr, view.key_ngrp = nullptr;
   view.gmask = nullptr, view.zone_vc = nullptr, view.zone_gsum = nullptr, view.prec = nullptr;
+  view.key_nspan = nullptr, view.gspan = nullptr, view.gsrc = nullptr;
   view.esc_rows = nullptr, view.lag_ct = nullptr, view.lag = nullptr, view.key_lag = nullptr;
   am_store *sub = nullptr;
   int rc = am_store_update_ex(c, view, V.ctr, dev_new, mask, mask ? tvc : nullptr, mask ? tpres : nullptr, d_gc_flags,
@@ -523,6 +532,7 @@ int am_store_grow_keys(am_ctx *c, const am_store *st, uint64_t n_new, const uint
   view.key_type = (uint8_t *)(b + o_type), view.key_flags = (uint8_t *)(b + o_flags);
   view.key_tbase = nullptr, view.rec_key_off = nullptr, view.rec_key_end = nullptr, view.key_ngrp = nullptr;
   view.gmask = nullptr, view.zone_vc = nullptr, view.zone_gsum = nullptr, view.prec = nullptr;
+  view.key_nspan = nullptr, view.gspan = nullptr, view.gsrc = nullptr;
   view.esc_rows = nullptr, view.lag_ct = nullptr, view.lag = nullptr, view.key_lag = nullptr;
   hipLaunchKernelGGL(k_grow_view, dim3(grid_threads(n_new + 1)), dim3(256), 0, c->stream, L,
                      (const uint64_t *)st->counter, n_new, (uint64_t *)view.key_off, (uint64_t *)view.key_end,

@@ -33,6 +33,8 @@
 //      wave ballots and their (a, b) pairs gathered into the output CSR -- already in the
 //      reference's order, no sort.
 // Reads with base-snapshot pairs, longer logs or ungrouped keys are handed to the next tier.
+// The split fresh read (k_grp_incl, then k_grp_spans) does step 2 over the group-span view: one
+// word per born group (birth op | kill op) instead of one record per birth and kill slot.
 #pragma once
 #include "am_block.h"
 
@@ -402,8 +404,9 @@ struct WgSmem {
 };
 
 template <int DMAX, int TYPE, bool GENERAL, bool PACKED, bool EXACT>
-__global__ void __launch_bounds__(WBLOCK, 4) k_grp_wg(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
+__global__ void __launch_bounds__(WBLOCK, 4) k_grp_wg(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
                                                       am_retry next) {
+  const am_op_log L = LA.log();
   constexpr int OPL = wopl<DMAX>();
   constexpr uint64_t TILE = (uint64_t)WBLOCK * OPL;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -817,9 +820,10 @@ __device__ bool base_merge(const am_op_log &L, const am_read_batch &B, am_read_r
 #define AM_WAVE_WAVES 4  // waves per SIMD the wave tier is compiled for
 #endif
 template <int DMAX, int TYPE, bool GENERAL, bool PACKED, bool EXACT, bool BM = false>
-__global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_op_log L, am_read_batch B, am_read_result R,
+__global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA, am_read_batch B, am_read_result R,
                                                                   am_sel S, am_retry next, uint32_t short_opl,
                                                                   GrpHint H, const uint32_t *ibm = nullptr) {
+  const am_op_log L = LA.log();
   constexpr int OPL = vopl<DMAX, PACKED>();
   constexpr uint64_t TILE = (uint64_t)WAVE * OPL;
   constexpr uint32_t LPW = 32 / OPL;  // lanes per bitmap word
@@ -1273,9 +1277,10 @@ __device__ __forceinline__ uint32_t incl_tile(const Ent &x, const PkRead<DMAX> &
 #define AM_INCL_WAVES 3  // waves per SIMD: the pipelined tile loop holds two tiles (168 VGPRs)
 #endif
 template <int DMAX, int TYPE, bool EXACT, bool LAG>
-__global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
+__global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
                                                        am_retry next, am_retry routed, uint32_t short_opl,
                                                        uint32_t *ibm) {
+  const am_op_log L = LA.log();
   constexpr int OPL = 4;
   constexpr uint64_t TILE = (uint64_t)WAVE * OPL;
   constexpr uint32_t LPW = 32 / OPL;
@@ -1533,10 +1538,23 @@ struct RPre {  // a read's prefetched inputs: one bitmap word and two record chu
   uint32_t w;
   u32x4 c[4];
 };
+// The record rule of a fresh read, one record: x (record i of its read, 0xFFFFFFFF: a dead slot)
+// against the read's LDS bitmap (bit = op + sh) sets its group's born or killed bit, a birth
+// also the group's birth record.  (k_grp_recs, and k_grp_spans for its keys without spans.)
+__device__ __forceinline__ void rec_apply(uint32_t x, uint32_t i, uint32_t sh, const uint32_t *incl, uint32_t *born,
+                                          uint32_t *killed, uint16_t *bri) {
+  if (x == 0xFFFFFFFFu) return;
+  const uint32_t bit = AM_REC_OP(x) + sh;
+  if (!((incl[bit >> 5] >> (bit & 31)) & 1u)) return;
+  const uint32_t g = AM_REC_GRP(x);
+  atomicOr(((x & AM_REC_KILL) ? killed : born) + (g >> 5), 1u << (g & 31));
+  if (!(x & AM_REC_KILL)) bri[g] = (uint16_t)i;  // a group's one birth
+}
 
 template <int DMAX, int TYPE>
-__global__ void __launch_bounds__(BLOCK, 5) k_grp_recs(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
+__global__ void __launch_bounds__(BLOCK, 5) k_grp_recs(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
                                                        uint32_t short_opl, const uint32_t *ibm) {
+  const am_op_log L = LA.log();
   __shared__ RSmem smem[NW];
   RSmem &s = smem[threadIdx.x >> 6];
   const uint32_t lane = threadIdx.x & (WAVE - 1);
@@ -1566,13 +1584,8 @@ __global__ void __launch_bounds__(BLOCK, 5) k_grp_recs(am_op_log L, am_read_batc
     const uint32_t xs[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const uint32_t x = xs[k];
-      if (x == 0xFFFFFFFFu || q + k < rk0 || q + k >= rk1) continue;
-      const uint32_t bit = AM_REC_OP(x) + sh;
-      if (!((s.incl[bit >> 5] >> (bit & 31)) & 1u)) continue;
-      const uint32_t g = AM_REC_GRP(x);
-      atomicOr(((x & AM_REC_KILL) ? s.killed : s.born) + (g >> 5), 1u << (g & 31));
-      if (!(x & AM_REC_KILL)) s.bri[g] = (uint16_t)(q + k - rk0);  // a group's one birth
+      if (xs[k] == 0xFFFFFFFFu || q + k < rk0 || q + k >= rk1) continue;
+      rec_apply(xs[k], (uint32_t)(q + k - rk0), sh, s.incl, s.born, s.killed, s.bri);
     }
   };
 
@@ -1670,6 +1683,194 @@ __global__ void __launch_bounds__(BLOCK, 5) k_grp_recs(am_op_log L, am_read_batc
   }
 }
 
+// ---------------------------------------------------------------- split fresh read, pass 2 by spans
+// k_grp_spans: k_grp_recs over the group-span view (include/antidote_mat.h key_nspan / gspan /
+// gsrc) -- one word per BORN group (birth op | kill op << 16) instead of one record per birth and
+// kill slot.  A fresh read has no base, so a group is alive iff its birth op is included and its
+// one effective kill (if any) is not; only an alive group reads its gsrc word (group | birth
+// record << 16) and sets its LDS bit: one atomicOr per survivor.  The batch structure, the
+// survivor listing and the pair gather are k_grp_recs's, and so are the outputs, bit for bit.
+// A read of a key without spans (AM_NSPAN_NONE: a group with two effective kills, ...) streams
+// the key's records here instead, k_grp_recs's born / killed rule without its prefetch: such
+// keys are rare (concurrent removes of one token), and a second launch for them, or a list of
+// them, costs every batch more than they do.
+constexpr int SPRE = 4;  // prefetched 16-byte span loads per lane: the first 1024 spans of a read
+struct SSlot {
+  uint64_t off0, rk0, ooff;
+  uint32_t r, nops, nb, G, ocap, nrec;  // nb == AM_NSPAN_NONE: by the nrec records
+};
+struct SSmem {
+  uint32_t alive[VG / 32], killed[VG / 32];  // (killed: the reads by records only)
+  uint32_t incl[VWORDS];
+  uint16_t list[RLIST];
+  uint16_t bri[VG];  // per alive group: its birth record (from the read's rk0)
+  SSlot slot[IWB];
+};
+struct SPre {  // a read's prefetched inputs: one bitmap word and SPRE span loads per lane
+  uint32_t w;
+  u32x4 c[SPRE];
+};
+
+template <int DMAX, int TYPE>
+__global__ void __launch_bounds__(BLOCK, 5) k_grp_spans(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
+                                                        uint32_t short_opl, const uint32_t *ibm) {
+  __shared__ SSmem smem[NW];
+  SSmem &s = smem[threadIdx.x >> 6];
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t sel0 = S.idx ? uniform_u32(S.range[0]) : 0u;
+  const uint64_t nsel = S.idx ? (uint64_t)(uniform_u32(S.range[1]) - sel0) : B.n_reads;
+  const uint64_t W = (uint64_t)gridDim.x * NW;
+  const uint64_t gw = (uint64_t)blockIdx.x * NW + uniform_u32(threadIdx.x >> 6);
+  const uint64_t *const pairs = L.prec ? L.prec : L.grp;
+  constexpr uint32_t SCH = (uint32_t)SPRE * 4 * WAVE;  // spans per pass of the wave
+
+  // spans [q0, q0 + SCH) of a read whose spans are [rk0, rk1) (lane i: four consecutive words per
+  // load, q0 a multiple of 4)
+  auto ld_spans = [&](uint64_t q0, uint64_t rk1, u32x4 (&c)[SPRE]) {
+#pragma unroll
+    for (int k = 0; k < SPRE; ++k) {
+      const uint64_t q = q0 + (uint64_t)k * 4 * WAVE + 4 * lane;
+      c[k] = q < rk1 ? *(const u32x4 *)(L.gspan + q) : u32x4{0, 0, 0, 0};
+    }
+  };
+  // prefetch read j of the slot table: bitmap words [t0 / 32, ...) (lane i: word i, the first
+  // 64), spans [rk0 & ~3, + SCH)
+  auto pre = [&](uint32_t j, SPre &p) {
+    const uint64_t off0 = s.slot[j].off0, rk0 = s.slot[j].rk0;
+    const uint32_t nops = s.slot[j].nops, nb = s.slot[j].nb;
+    const uint64_t t0 = off0 & ~31ull;
+    const uint32_t nw = (uint32_t)((off0 + nops - t0 + 31) / 32);
+    p.w = lane < nw ? ibm[(t0 >> 5) + lane] : 0u;
+    ld_spans(rk0 & ~3ull, rk0 + (nb == AM_NSPAN_NONE ? 0u : nb), p.c);
+  };
+  // one pass of spans against the LDS bitmap (bit = op + sh): the alive ones' gsrc words are
+  // loaded together (independent loads, one wait), then their bits and birth records set
+  auto apply = [&](const u32x4 (&c)[SPRE], uint64_t q0, uint64_t rk0, uint64_t rk1, uint32_t sh) {
+    uint32_t src[SPRE * 4];
+    uint32_t am = 0;
+#pragma unroll
+    for (int k = 0; k < SPRE; ++k) {
+      const uint64_t q = q0 + (uint64_t)k * 4 * WAVE + 4 * lane;
+      const uint32_t xs[4] = {c[k].x, c[k].y, c[k].z, c[k].w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool inr = q + e >= rk0 && q + e < rk1;  // (a word of a neighbouring key is not looked at)
+        const uint32_t x = inr ? xs[e] : 0u;
+        const uint32_t b = (x & 0xFFFFu) + sh, kl = (x >> 16) + sh;
+        const bool inb = (s.incl[b >> 5] >> (b & 31)) & 1u, ink = (s.incl[kl >> 5] >> (kl & 31)) & 1u;
+        const bool al = inr && inb && (kl == b || !ink);
+        src[4 * k + e] = al ? L.gsrc[q + e] : 0u;
+        am |= (uint32_t)al << (4 * k + e);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < SPRE * 4; ++i)
+      if ((am >> i) & 1u) {
+        const uint32_t g = src[i] & 0xFFFFu;
+        atomicOr(s.alive + (g >> 5), 1u << (g & 31));
+        s.bri[g] = (uint16_t)(src[i] >> 16);  // a group's one birth
+      }
+  };
+
+  for (uint64_t b0 = gw * IWB; b0 < nsel; b0 += (uint64_t)IWB * W) {
+    // ---- lane j < IWB: read b0 + j -> slot j (the reads k_grp_incl took and left ok) ----
+    const uint64_t ii = b0 + lane;
+    bool ok = false;
+    if (lane < IWB && ii < nsel) {
+      GMeta mm;
+      read_meta(L, B, S.idx ? (uint64_t)S.idx[sel0 + ii] : ii, TYPE, mm);
+      ok = mm.st == AM_OK && wave_takes(L, B, mm, short_opl) && R.status[mm.r] == AM_OK;
+      if (ok) {
+        const uint32_t nb = L.key_nspan[mm.key];
+        SSlot &w = s.slot[lane];
+        const uint64_t o0 = R.value.set_off[mm.r], o1 = R.value.set_off[mm.r + 1];
+        w.off0 = mm.off0, w.rk0 = mm.rk0, w.ooff = o0;
+        w.r = (uint32_t)mm.r, w.nops = (uint32_t)(mm.off1 - mm.off0), w.nrec = (uint32_t)(mm.rk1 - mm.rk0);
+        // (a count beyond the key's record slots is no span view)
+        w.nb = nb > w.nrec ? AM_NSPAN_NONE : nb;
+        w.G = mm.G, w.ocap = o1 - o0 < 0xFFFFFFFFull ? (uint32_t)(o1 - o0) : 0xFFFFFFFFu;
+      }
+    }
+    uint64_t em = __ballot(ok);
+    wave_sync();
+    SPre cur;
+    if (em) pre((uint32_t)__builtin_ctzll(em), cur);
+    uint32_t setlen = 0;  // lane j: read j's survivor count
+    int32_t cap_err = 0;  // lane j: read j overflowed its capacity
+    for (; em; em &= em - 1) {
+      const uint32_t j = (uint32_t)__builtin_ctzll(em);
+      const uint64_t off0 = uniform_u64(s.slot[j].off0), rk0 = uniform_u64(s.slot[j].rk0);
+      const uint32_t nbj = uniform_u32(s.slot[j].nb);
+      const bool byrec = nbj == AM_NSPAN_NONE;
+      const uint64_t off1 = off0 + uniform_u32(s.slot[j].nops), rk1 = rk0 + (byrec ? 0u : nbj);
+      const uint32_t G = uniform_u32(s.slot[j].G);
+      const uint64_t t0 = off0 & ~31ull;
+      const uint32_t sh = (uint32_t)(off0 - t0), nw = (uint32_t)((off1 - t0 + 31) / 32);
+      // this read's bitmap into LDS (words past the first 64 straight from memory: long logs)
+      if (lane < nw) s.incl[lane] = cur.w;
+      for (uint32_t i = WAVE + lane; i < nw; i += WAVE) s.incl[i] = ibm[(t0 >> 5) + i];
+      for (uint32_t g = lane; g < (G + 31) / 32; g += WAVE) s.alive[g] = 0, s.killed[g] = 0;
+      u32x4 c[SPRE];
+#pragma unroll
+      for (int k = 0; k < SPRE; ++k) c[k] = cur.c[k];
+      // the next read's inputs in flight from here on
+      const uint64_t rest = em & (em - 1);
+      if (rest) pre((uint32_t)__builtin_ctzll(rest), cur);
+      wave_sync();
+      // ---- spans: the prefetched pass, then the rest a pass at a time ----
+      const uint64_t qa = rk0 & ~3ull;
+      apply(c, qa, rk0, rk1, sh);
+      for (uint64_t q0 = qa + SCH; q0 < rk1; q0 += SCH) {
+        ld_spans(q0, rk1, c);
+        apply(c, q0, rk0, rk1, sh);
+      }
+      if (byrec) {  // rare: the key's records by k_grp_recs's rule, then alive = born and not killed
+        const uint32_t nrec = uniform_u32(s.slot[j].nrec);
+        for (uint32_t i = lane; i < nrec; i += WAVE)
+          rec_apply(L.rec_g[rk0 + i], i, sh, s.incl, s.alive, s.killed, s.bri);
+        wave_sync();
+        for (uint32_t g = lane; g < (G + 31) / 32; g += WAVE) s.alive[g] &= ~s.killed[g];
+      }
+      wave_sync();
+      // ---- survivors in group order: lane w owns alive word w; listed in rounds of RLIST ----
+      const uint32_t nwd = (G + 31) / 32;
+      const uint32_t aw = lane < nwd ? s.alive[lane] : 0u;
+      const uint32_t cnt = (uint32_t)__popc(aw);
+      const uint32_t inc = wave_incl_scan_u32(cnt, lane);
+      const uint32_t ns = (uint32_t)__shfl((int)inc, 63, WAVE);
+      const uint64_t ooff = uniform_u64(s.slot[j].ooff);
+      const uint32_t ocap = uniform_u32(s.slot[j].ocap);
+      const uint32_t nput = ns < ocap ? ns : ocap;
+      for (uint32_t base = 0; base < nput; base += RLIST) {
+        uint32_t o = inc - cnt;
+        for (uint32_t bits = aw; bits; bits &= bits - 1, ++o)
+          if (o >= base && o < base + RLIST) s.list[o - base] = (uint16_t)(lane * 32 + __builtin_ctz(bits));
+        wave_sync();
+        const uint32_t end = nput - base < RLIST ? nput - base : RLIST;
+        for (uint32_t j0 = 0; j0 < end; j0 += 2 * WAVE) {
+          const uint32_t j1 = j0 + lane, j2 = j1 + WAVE;
+          u64x2 p1 = {0, 0}, p2 = {0, 0};
+          // a survivor's pair through its birth record (prec), as in k_grp_recs
+          if (j1 < end) p1 = *(const u64x2 *)(pairs + 2 * (rk0 + (L.prec ? s.bri[s.list[j1]] : s.list[j1])));
+          if (j2 < end) p2 = *(const u64x2 *)(pairs + 2 * (rk0 + (L.prec ? s.bri[s.list[j2]] : s.list[j2])));
+          if (j1 < end) R.value.set_a[ooff + base + j1] = p1.x, R.value.set_b[ooff + base + j1] = p1.y;
+          if (j2 < end) R.value.set_a[ooff + base + j2] = p2.x, R.value.set_b[ooff + base + j2] = p2.y;
+        }
+        wave_sync();
+      }
+      if (lane == j) setlen = ns, cap_err = ns > ocap;
+      wave_sync();
+    }
+    // ---- the batch's outputs (lane j: read b0 + j): set_len, or the capacity status ----
+    if (ok) {
+      const uint64_t r = s.slot[lane].r;
+      if (cap_err) R.status[r] = AM_ERR_CAPACITY;
+      else R.value.set_len[r] = setlen;
+    }
+    wave_sync();  // the slots are rewritten by the next batch
+  }
+}
+
 // ---------------------------------------------------------------- 16-lane row per short read
 // A wave takes 64 reads at a time: lane i checks read i against the row limits (the others
 // leave through one hand-off atomic per wave), then the four 16-lane rows walk the
@@ -1682,8 +1883,9 @@ struct RowGSmem {
 };
 
 template <int DMAX, int TYPE, bool GENERAL, bool PACKED, bool EXACT>
-__global__ void __launch_bounds__(BLOCK) k_grp_row(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
+__global__ void __launch_bounds__(BLOCK) k_grp_row(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
                                                    am_retry next) {
+  const am_op_log L = LA.log();
   __shared__ RowGSmem rsm[BLOCK / RG];
   RowGSmem &s = rsm[threadIdx.x / RG];
   const uint32_t lane = threadIdx.x & (WAVE - 1), row = lane / RG, sl = lane % RG;
@@ -1833,7 +2035,8 @@ __global__ void __launch_bounds__(BLOCK) k_grp_row(am_op_log L, am_read_batch B,
 
 // ---------------------------------------------------------------- launchers
 // the split fresh read: k_grp_incl (op stream -> inclusion bitmap + scalars), then the record /
-// survivor pass k_grp_recs
+// survivor pass: k_grp_spans when the log has the group-span view (key_nspan, gspan and gsrc all
+// set; a caller that nulls one gets k_grp_recs), else k_grp_recs
 template <int D, int TYPE, bool EXACT>
 int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_read_result *R, am_sel S,
                  am_retry next, uint32_t short_opl) {
@@ -1842,19 +2045,23 @@ int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_rea
   if (int rc = am_ctx_scratch(ctx, AM_SCR_INCL, (stride / 32 + 4) * 4, &ibm)) return rc;
   // the lag view when the log has it: 4 + 2 D bytes of commit vector per op instead of 4 D
   const bool lag = L->lag_ct && L->lag && L->key_lag;
-  static int occ_i = 0, occ_w = 0;
+  const bool spans = L->key_nspan && L->gspan && L->gsrc;
+  static int occ_i = 0, occ_w = 0, occ_s = 0;  // per kernel: each grid is sized by its own
   if (!occ_i) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_i, k_grp_incl<D, TYPE, EXACT, true>, BLOCK, 0) !=
             hipSuccess ||
         occ_i < 1)
       occ_i = 2;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_w, k_grp_recs<D, TYPE>, BLOCK, 0) != hipSuccess ||
-        occ_w < 1)
-      occ_w = 1;
+  }
+  int &occ_r = spans ? occ_s : occ_w;  // the record pass that runs
+  if (!occ_r) {
+    const hipError_t e = spans ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_r, k_grp_spans<D, TYPE>, BLOCK, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_r, k_grp_recs<D, TYPE>, BLOCK, 0);
+    if (e != hipSuccess || occ_r < 1) occ_r = 1;
   }
   const uint64_t want_i = (B->n_reads + NW * IWB - 1) / (NW * IWB), want_w = want_i;
   const uint64_t bi = want_i < (uint64_t)ctx->n_cu * occ_i ? want_i : (uint64_t)ctx->n_cu * occ_i;
-  const uint64_t bw = want_w < (uint64_t)ctx->n_cu * occ_w ? want_w : (uint64_t)ctx->n_cu * occ_w;
+  const uint64_t bw = want_w < (uint64_t)ctx->n_cu * occ_r ? want_w : (uint64_t)ctx->n_cu * occ_r;
   if (bi == 0) return AM_OK;
   if (lag) {
     // the reads of packed-routed keys leave the lag instantiation through a list; the packed
@@ -1870,8 +2077,13 @@ int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_rea
     hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B,
                        *R, S, next, am_retry{}, short_opl, (uint32_t *)ibm);
   }
-  hipLaunchKernelGGL((k_grp_recs<D, TYPE>), dim3((unsigned)bw), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S,
-                     short_opl, (const uint32_t *)ibm);
+  if (spans) {
+    hipLaunchKernelGGL((k_grp_spans<D, TYPE>), dim3((unsigned)bw), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S,
+                       short_opl, (const uint32_t *)ibm);
+  } else {
+    hipLaunchKernelGGL((k_grp_recs<D, TYPE>), dim3((unsigned)bw), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S,
+                       short_opl, (const uint32_t *)ibm);
+  }
   AM_HIP(hipGetLastError());
   return AM_OK;
 }

@@ -55,8 +55,14 @@ struct BuildSmem {
   uint64_t val[RCAP], tok[RCAP];  // per record: AW elem / MV value (0 for kills), token
   uint32_t grpof[RCAP];         // per record: raw group (kill-key order)
   uint32_t bc[RCAP], bfirst[RCAP], rep[RCAP], fin[RCAP];  // per raw group
+  uint32_t nkill[RCAP], kop[RCAP];  // per raw group: its effective kill records, and the op of one
   uint32_t wsum[NW];
-  uint32_t ctr[4];              // [1] outside the closed form
+  uint32_t ctr[4];              // [1] outside the closed form; [2] a group with two effective kills
+};
+
+// the group-span view's columns (all three, or all null: not built)
+struct SpanOut {
+  uint32_t *nspan, *gspan, *gsrc;
 };
 
 struct BuildSink {
@@ -106,7 +112,7 @@ __device__ uint32_t raw_groups(BuildSmem &s, uint32_t n) {
 template <int TYPE>
 __device__ void build_key(const am_op_log &L, BuildSmem &s, uint64_t k, uint64_t off0, uint64_t off1, uint64_t r0,
                           uint32_t n, const uint64_t *rcnt, uint32_t *rec_g, uint64_t *grp,
-                          uint32_t *ngrp, uint64_t *prec) {
+                          uint32_t *ngrp, uint64_t *prec, SpanOut sp) {
   const uint32_t tid = threadIdx.x;
   // 1. the key's births / kills into LDS (record order = op order, effect order within an op)
   for (uint64_t p = off0 + tid; p < off1; p += BLOCK) {
@@ -115,7 +121,7 @@ __device__ void build_key(const am_op_log &L, BuildSmem &s, uint64_t k, uint64_t
     BuildSink sk{&s, (uint32_t)(rcnt[p] - r0), (uint32_t)(p - off0)};
     set_effects<TYPE>(L, p, meta, 0, sk);
   }
-  if (tid == 0) s.ctr[1] = 0;
+  if (tid == 0) s.ctr[1] = 0, s.ctr[2] = 0;
   __syncthreads();
   // 2. sort by kill key: AW (elem, token), MV token
   for (uint32_t i = tid; i < n; i += BLOCK) {
@@ -142,7 +148,10 @@ __device__ void build_key(const am_op_log &L, BuildSmem &s, uint64_t k, uint64_t
     }
   __syncthreads();
   if (s.ctr[1]) {
-    if (tid == 0) ngrp[k] = AM_NGRP_NONE;
+    if (tid == 0) {
+      ngrp[k] = AM_NGRP_NONE;
+      if (sp.nspan) sp.nspan[k] = AM_NSPAN_NONE;
+    }
     __syncthreads();
     return;
   }
@@ -159,6 +168,7 @@ __device__ void build_key(const am_op_log &L, BuildSmem &s, uint64_t k, uint64_t
       s.kb[g] = s.tok[rp];
     }
     s.kp[g] = (int32_t)g;
+    s.nkill[g] = 0;
   }
   __syncthreads();
   block_sort(s.ka, s.kb, s.kp, G, RCAP);
@@ -180,6 +190,10 @@ __device__ void build_key(const am_op_log &L, BuildSmem &s, uint64_t k, uint64_t
     const bool kill = (s.info[r] & KILL31) != 0;
     const bool keep = !kill || b == 0xFFFFFFFFu || op > (s.info[b] & 0xFFFFu);
     rec_g[r0 + r] = keep ? (op | ((kill ? 1u : 0u) << 16) | (s.fin[g] << 17)) : 0xFFFFFFFFu;
+    if (kill && keep && b != 0xFFFFFFFFu) {  // an effective kill of a born group: its count and op
+      atomicAdd(&s.nkill[g], 1u);
+      s.kop[g] = op;
+    }
     if (prec && !kill) {  // a birth's (elem | value, token) is its group's pair
       prec[2 * (r0 + r)] = s.val[r];
       prec[2 * (r0 + r) + 1] = s.tok[r];
@@ -187,10 +201,39 @@ __device__ void build_key(const am_op_log &L, BuildSmem &s, uint64_t k, uint64_t
   }
   if (tid == 0) ngrp[k] = G;
   __syncthreads();
+  // the group-span view (include/antidote_mat.h): one word per born group, in birth (record)
+  // order -- a ballot scan over the records ranks the births
+  if (!sp.nspan) return;
+  const uint32_t w = tid >> 6, l = tid & 63;
+  const uint64_t lt = (1ull << l) - 1ull;
+  uint32_t nb = 0;
+  for (uint32_t c = 0; c < n; c += BLOCK) {
+    const uint32_t r = c + tid;
+    const bool birth = r < n && !(s.info[r] & KILL31);
+    const uint64_t m = __ballot(birth);
+    if (l == 0) s.wsum[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t woff = 0, total = 0;
+    for (int v = 0; v < NW; ++v) {
+      if (v < (int)w) woff += s.wsum[v];
+      total += s.wsum[v];
+    }
+    if (birth) {
+      const uint32_t g = s.grpof[r], op = s.info[r] & 0xFFFFu, nk = s.nkill[g];
+      const uint32_t i = nb + woff + (uint32_t)__popcll(m & lt);
+      if (nk > 1) s.ctr[2] = 1;  // concurrent removes of one token: the key keeps the record path
+      sp.gspan[r0 + i] = op | ((nk ? s.kop[g] : op) << 16);
+      sp.gsrc[r0 + i] = s.fin[g] | (r << 16);
+    }
+    nb += total;
+    __syncthreads();
+  }
+  if (tid == 0) sp.nspan[k] = (s.ctr[2] || off1 - off0 >= 65535) ? AM_NSPAN_NONE : nb;
+  __syncthreads();
 }
 
 __global__ void __launch_bounds__(BLOCK) k_grp_build(am_op_log L, const uint64_t *rcnt, uint32_t *rec_g, uint64_t *grp,
-                                                     uint32_t *ngrp, uint64_t *prec) {
+                                                     uint32_t *ngrp, uint64_t *prec, SpanOut sp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   BuildSmem &s = *reinterpret_cast<BuildSmem *>(smem_raw);
   for (uint64_t k = blockIdx.x; k < L.n_keys; k += gridDim.x) {
@@ -201,11 +244,14 @@ __global__ void __launch_bounds__(BLOCK) k_grp_build(am_op_log L, const uint64_t
     const uint64_t n = r1 - r0;
     const bool set = type == AM_AWSET || type == AM_MVREG;
     if (!set || n > RCAP || off1 - off0 >= 65536 || (kfl & AM_KEY_MIXED_TYPES) || am_big_grp_key(L, k)) {
-      if (threadIdx.x == 0) ngrp[k] = AM_NGRP_NONE;
+      if (threadIdx.x == 0) {
+        ngrp[k] = AM_NGRP_NONE;
+        if (sp.nspan) sp.nspan[k] = AM_NSPAN_NONE;
+      }
       continue;
     }
-    if (type == AM_AWSET) build_key<AM_AWSET>(L, s, k, off0, off1, r0, (uint32_t)n, rcnt, rec_g, grp, ngrp, prec);
-    else build_key<AM_MVREG>(L, s, k, off0, off1, r0, (uint32_t)n, rcnt, rec_g, grp, ngrp, prec);
+    if (type == AM_AWSET) build_key<AM_AWSET>(L, s, k, off0, off1, r0, (uint32_t)n, rcnt, rec_g, grp, ngrp, prec, sp);
+    else build_key<AM_MVREG>(L, s, k, off0, off1, r0, (uint32_t)n, rcnt, rec_g, grp, ngrp, prec, sp);
   }
 }
 
@@ -229,8 +275,9 @@ int am_launch_group(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_
 }
 
 int am_launch_group_build(am_ctx *ctx, const am_op_log *L, const uint64_t *rcnt, uint32_t *rec_g, uint64_t *grp,
-                          uint32_t *key_ngrp, uint64_t *prec) {
+                          uint32_t *key_ngrp, uint64_t *prec, uint32_t *key_nspan, uint32_t *gspan, uint32_t *gsrc) {
   if (L->n_keys == 0) return AM_OK;
+  const bool spans = key_nspan && gspan && gsrc;
   constexpr size_t smem = sizeof(BuildSmem);
   static bool attr = false;
   if (!attr) {
@@ -239,7 +286,7 @@ int am_launch_group_build(am_ctx *ctx, const am_op_log *L, const uint64_t *rcnt,
   }
   const uint64_t blocks = L->n_keys < (uint64_t)ctx->n_cu * 8 ? L->n_keys : (uint64_t)ctx->n_cu * 8;
   hipLaunchKernelGGL(k_grp_build, dim3((unsigned)blocks), dim3(BLOCK), smem, ctx->stream, *L, rcnt, rec_g, grp,
-                     key_ngrp, prec);
+                     key_ngrp, prec, spans ? SpanOut{key_nspan, gspan, gsrc} : SpanOut{nullptr, nullptr, nullptr});
   AM_HIP(hipGetLastError());
   return AM_OK;
 }

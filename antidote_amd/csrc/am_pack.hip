@@ -414,6 +414,7 @@ int build_records(am_store *st) {
   }
   rc = AM_OK;
   void *rko = nullptr, *rke = nullptr, *rg = nullptr, *gp = nullptr, *ng = nullptr, *pr = nullptr;
+  void *ns = nullptr, *gs = nullptr, *gr = nullptr;  // the group-span view: key_nspan, gspan, gsrc
   rc = am_dev_alloc(c, (d.n_keys + 1) * 8, &rko);
   if (!rc) st->allocs.push_back(rko);
   if (!rc && d.key_end) {
@@ -424,14 +425,20 @@ int build_records(am_store *st) {
   if (!rc) st->allocs.push_back(rg), rc = am_dev_alloc(c, (n_rec + 4) * 16, &gp);
   if (!rc) st->allocs.push_back(gp), rc = am_dev_alloc(c, (d.n_keys + 1) * 4, &ng);
   if (!rc) st->allocs.push_back(ng), rc = am_dev_alloc(c, (n_rec + 4) * 16, &pr);
-  if (!rc) st->allocs.push_back(pr);
+  if (!rc) st->allocs.push_back(pr), rc = am_dev_alloc(c, (d.n_keys + 1) * 4, &ns);
+  if (!rc) st->allocs.push_back(ns), rc = am_dev_alloc(c, (n_rec + 4) * 4, &gs);
+  if (!rc) st->allocs.push_back(gs), rc = am_dev_alloc(c, (n_rec + 4) * 4, &gr);
+  if (!rc) st->allocs.push_back(gr);
+  // keys no builder gives spans (other types, ungrouped, chunked) stay at AM_NSPAN_NONE
+  if (!rc && hipMemsetAsync(ns, 0xFF, (d.n_keys + 1) * 4, c->stream) != hipSuccess) rc = AM_ERR_HIP;
   if (!rc) {
     hipLaunchKernelGGL(k_rec_key_off, dim3(grid_of(d.n_keys + 1)), dim3(256), 0, c->stream, d.key_off, d.key_end,
                        d.n_keys, cnt, (uint64_t *)rko, (uint64_t *)rke);
     am_op_log v = d;
     v.rec_key_off = (const uint64_t *)rko;
     v.rec_key_end = (const uint64_t *)rke;
-    rc = am_launch_group_build(c, &v, cnt, (uint32_t *)rg, (uint64_t *)gp, (uint32_t *)ng, (uint64_t *)pr);
+    rc = am_launch_group_build(c, &v, cnt, (uint32_t *)rg, (uint64_t *)gp, (uint32_t *)ng, (uint64_t *)pr,
+                               (uint32_t *)ns, (uint32_t *)gs, (uint32_t *)gr);
     if (!rc) rc = am_launch_group_build_big(c, &v, cnt, (uint32_t *)rg, (uint64_t *)gp, (uint32_t *)ng);
     if (!rc && (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) {
       am_set_error("token-group view: build pass failed");
@@ -464,6 +471,7 @@ int build_records(am_store *st) {
   d.grp = (const uint64_t *)gp;
   d.key_ngrp = (const uint32_t *)ng;
   d.prec = (const uint64_t *)pr;
+  d.key_nspan = (const uint32_t *)ns, d.gspan = (const uint32_t *)gs, d.gsrc = (const uint32_t *)gr;
   d.gmask = (const uint64_t *)gmk;
   return AM_OK;
 }

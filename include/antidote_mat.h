@@ -72,7 +72,7 @@
 extern "C" {
 #endif
 
-#define AM_ABI_VERSION 13
+#define AM_ABI_VERSION 14
 #define AM_MAX_DC 32
 
 /* CRDT types (the reference's type atoms) */
@@ -275,6 +275,23 @@ typedef struct am_op_log {
   const uint32_t *lag_ct;      /* [snap_stride]                                       */
   const uint16_t *lag;         /* [n_dc][snap_stride]                                 */
   const int32_t *key_lag;      /* [n_keys][n_dc]                                      */
+  /* Group-span view (ABI 14; device stores with the token-group view, or NULL): a FRESH read (no
+   * base snapshot) keeps a group iff its birth op is included and none of its effective kills
+   * is, and in a causal history a token has at most one effective kill, so one word per BORN
+   * group holds what the read needs.  key_nspan[k] = NB, the number of born groups of key k, or
+   * AM_NSPAN_NONE when the key has no span view (key_ngrp[k] is AM_NGRP_NONE or carries
+   * AM_NGRP_BIG, a group has two or more effective kill records, or the key has 65535 or more
+   * ops): such a key is read through rec_g.  The spans reuse the record offsets (NB <= the key's
+   * record slots, append room included): for the i-th birth of key k in record (= op) order,
+   *   gspan[rec_key_off[k] + i] = birth op | kill op << 16   (op indices within the key; kill
+   *                               op == birth op: no effective kill -- one always has a later op)
+   *   gsrc[rec_key_off[k] + i]  = group index (its output rank, the g of grp) | birth record
+   *                               index << 16 (the record of prec), read for survivors only
+   * Every reader gives the same result with any of the three NULL (then through rec_g).
+   * Maintained by every writer (am_store_apply copies a touched key's spans and key_nspan). */
+  const uint32_t *key_nspan;   /* [n_keys]                                            */
+  const uint32_t *gspan;       /* [n_rec]                                             */
+  const uint32_t *gsrc;        /* [n_rec]                                             */
 } am_op_log;
 #define AM_ZONE_OPS 256u
 #define AM_GMASK_MAX_GRP 32u
@@ -282,6 +299,7 @@ typedef struct am_op_log {
 #define AM_REC_OP(m) ((m) & 0xFFFFu)
 #define AM_REC_GRP(m) ((m) >> 17)
 #define AM_NGRP_NONE 0xFFFFFFFFu
+#define AM_NSPAN_NONE 0xFFFFFFFFu
 #define AM_GRP_MAX_REC 2048u
 /* Chunked token-group view of a hot MV-register key (more than AM_BIG_MIN_OPS ops): its groups
  * are built with device-wide sorts instead of one workgroup's LDS, key_ngrp[k] = G |
