@@ -89,6 +89,14 @@ class am_read_result(ctypes.Structure):
     ]
 
 
+class am_writeset(ctypes.Structure):
+    _fields_ = [
+        ("n_ws", c_uint64), ("n_eff", c_uint64), ("n_var", c_uint64),
+        ("row", c_void_p), ("type", c_void_p), ("eff_off", c_void_p), ("eff_meta", c_void_p),
+        ("p0", c_void_p), ("p1", c_void_p), ("var_off", c_void_p), ("var_data", c_void_p),
+    ]
+
+
 class am_synth_params(ctypes.Structure):
     _fields_ = [
         ("seed", c_uint64), ("n_keys", c_uint64), ("ops_per_key", c_uint32), ("n_dc", c_uint32),
@@ -116,6 +124,10 @@ AM_SNAPCACHE_ABSENT = 0xFFFFFFFF
 AM_GC_PRUNED_ALL = 0x1
 AM_GC_TRIGGER = 0x2
 AM_OPS_THRESHOLD = 50
+# am_materialize_eager: one entry's write-set limits and the two kernel shapes (AM_EAGER_*)
+AM_EAGER_MAX_BIRTHS, AM_EAGER_MAX_KILLS, AM_EAGER_MAX_EFFECTS = 1024, 2048, 32767
+AM_EAGER_TILE_WAVE, AM_EAGER_TILE_WG = 64, 256
+AM_EAGER_SMALL_WORDS, AM_EAGER_SMALL_SLOTS = 128, 128
 
 
 # (name, restype, argtypes) of every exported symbol declared in include/antidote_mat.h
@@ -183,6 +195,14 @@ SIGNATURES = [
     ("am_read_objects_submit", c_int, [c_void_p, c_uint32, c_void_p, c_void_p, POINTER(am_read_batch),
                                        POINTER(am_read_result), POINTER(c_void_p)]),
     ("am_ticket_wait", c_int, [c_void_p]),
+    ("am_materialize_eager", c_int, [c_void_p, c_uint32, POINTER(am_writeset), POINTER(am_values), c_void_p,
+                                     POINTER(am_values), c_void_p]),
+    ("am_materialize_eager_host", c_int, [c_void_p, c_uint32, POINTER(am_writeset), POINTER(am_values), c_void_p,
+                                          POINTER(am_values), c_void_p]),
+    ("am_read_objects_ws_host", c_int, [c_void_p, c_uint32, c_void_p, c_void_p, POINTER(am_read_batch),
+                                        POINTER(am_writeset), POINTER(am_read_result)]),
+    ("am_read_objects_ws_submit", c_int, [c_void_p, c_uint32, c_void_p, c_void_p, POINTER(am_read_batch),
+                                          POINTER(am_writeset), POINTER(am_read_result), POINTER(c_void_p)]),
     ("am_codec_create", c_int, [POINTER(c_void_p)]),
     ("am_codec_destroy", c_int, [c_void_p]),
     ("am_codec_intern", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
@@ -229,7 +249,7 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
-        if L.am_abi_version() != 14:
+        if L.am_abi_version() != 15:
             raise AmError("ABI version mismatch")
         _lib = L
     return _lib

@@ -13,7 +13,7 @@
 
 #include "../../include/antidote_mat.h"
 
-enum { AM_SCR_PLAN = 0, AM_SCR_BIGMETA = 1, AM_SCR_BIGREC = 2, AM_SCR_ROWS = 3, AM_SCR_GRP = 4, AM_SCR_SPARE = 5, AM_SCR_SNAP = 6, AM_SCR_GC = 7, AM_SCR_SIZES = 8, AM_SCR_MISC = 9, AM_SCR_INCL = 10, AM_SCR_ROUTE = 11, AM_N_SCR = 12 };
+enum { AM_SCR_PLAN = 0, AM_SCR_BIGMETA = 1, AM_SCR_BIGREC = 2, AM_SCR_ROWS = 3, AM_SCR_GRP = 4, AM_SCR_SPARE = 5, AM_SCR_SNAP = 6, AM_SCR_GC = 7, AM_SCR_SIZES = 8, AM_SCR_MISC = 9, AM_SCR_INCL = 10, AM_SCR_ROUTE = 11, AM_SCR_EAGER = 12, AM_N_SCR = 13 };
 
 struct am_ctx {
   int device = 0;
@@ -225,6 +225,12 @@ struct am_snapcache;
 extern "C" int am_snapcache_grow(am_snapcache *c, uint64_t new_n);  // am_snapcache.hip (not exported in the header)
 int am_store_key_lens(am_ctx *c, const am_store *st, uint64_t m, const uint64_t *d_keys, const uint8_t *flags_full,
                       uint64_t *h_len, uint8_t *h_flags);
+
+// materialize_eager/3 over a device result (am_eager.hip): the value and status of the rows a host
+// write set names (rows of dr; capacities from dr's set_off, whose host copy is host_set_off)
+// are replaced by the eager result, on the context stream.  am_vnode.hip's read_objects path.
+int am_eager_apply_result(am_ctx *ctx, uint32_t n_dc, const am_writeset *host_ws, const uint64_t *host_set_off,
+                          am_read_result *dr);
 
 // Short-read tier (am_rows.hip): reads with at most short_max ops (and error reads) are
 // materialized by one 16-lane row each.  list/count (set types only): reads the tier

@@ -203,16 +203,23 @@ int grow_keys(am_vnode *v, uint64_t new_n) {
 
 struct ReadArg {
   am_vnode *v;
+  const am_writeset *ws;       // the reading transaction's own effects (host; rows of this round), or null
+  const uint64_t *host_set_off;  // the result's set capacities (host copy)
 };
 int run_round(void *arg, const am_read_batch *db, am_read_result *dr, const void *extra_dev) {
-  am_vnode *v = static_cast<ReadArg *>(arg)->v;
-  return am_snapcache_read_gc(v->ctx, v->sc, &v->st->dev, db, (const uint8_t *)extra_dev, dr, v->gc_mask, v->thr_vc,
-                              v->thr_pres);
+  const ReadArg *a = static_cast<ReadArg *>(arg);
+  am_vnode *v = a->v;
+  int rc = am_snapcache_read_gc(v->ctx, v->sc, &v->st->dev, db, (const uint8_t *)extra_dev, dr, v->gc_mask, v->thr_vc,
+                                v->thr_pres);
+  // apply_tx_updates_to_snapshot/4 on the device result, before it is copied back
+  if (!rc && a->ws && a->ws->n_ws) rc = am_eager_apply_result(v->ctx, v->n_dc, a->ws, a->host_set_off, dr);
+  return rc;
 }
 
 // one round of reads over distinct keys (host arrays), then the GCs they triggered
-int read_round(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, am_read_result *hr) {
-  ReadArg a{v};
+int read_round(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, am_read_result *hr,
+               const am_writeset *ws = nullptr) {
+  ReadArg a{v, ws, hr->value.set_off};
   const uint64_t n = hb->n_reads;
   std::vector<uint8_t> sg(n, 0);
   if (should_gc) std::copy(should_gc, should_gc + n, sg.begin());
@@ -508,13 +515,66 @@ int am_vnode_insert_host(am_vnode *v, const am_op_log *h) {
   return insert_keys(v, *h, keys, keys, beg, end);
 }
 
-int am_vnode_read_host(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, am_read_result *hr) {
+}  // extern "C"
+
+namespace {
+
+// the entries of a host write set whose rows a round serves, rows renumbered to the round's
+struct WsRound {
+  am_writeset ws{};
+  std::vector<uint64_t> row, eff_off, p0, p1, var_off, var_data;
+  std::vector<uint8_t> type, meta;
+  WsRound(const am_writeset &h, const std::vector<uint64_t> &sel) {
+    std::vector<uint64_t> at(sel.empty() ? 0 : *std::max_element(sel.begin(), sel.end()) + 1, ~0ull);
+    for (uint64_t q = 0; q < sel.size(); ++q) at[sel[q]] = q;
+    eff_off.push_back(0);
+    if (h.var_off) var_off.push_back(0);
+    for (uint64_t i = 0; i < h.n_ws; ++i) {
+      if (h.row[i] >= at.size() || at[h.row[i]] == ~0ull) continue;
+      row.push_back(at[h.row[i]]), type.push_back(h.type[i]);
+      for (uint64_t p = h.eff_off[i]; p < h.eff_off[i + 1]; ++p) {
+        meta.push_back(h.eff_meta[p]), p0.push_back(h.p0[p]), p1.push_back(h.p1[p]);
+        if (h.var_off) {
+          for (uint64_t w = h.var_off[p]; w < h.var_off[p + 1]; ++w) var_data.push_back(h.var_data[w]);
+          var_off.push_back(var_data.size());
+        }
+      }
+      eff_off.push_back(meta.size());
+    }
+    ws.n_ws = row.size(), ws.n_eff = meta.size(), ws.n_var = var_data.size();
+    meta.push_back(0), p0.push_back(0), p1.push_back(0), var_data.push_back(0);  // non-null when empty
+    ws.row = row.data(), ws.type = type.data(), ws.eff_off = eff_off.data(), ws.eff_meta = meta.data();
+    ws.p0 = p0.data(), ws.p1 = p1.data();
+    if (h.var_off) ws.var_off = var_off.data(), ws.var_data = var_data.data();
+  }
+};
+
+bool ws_valid(const am_writeset *ws, uint64_t n_reads) {
+  if (!ws || ws->n_ws == 0) return true;
+  if (!ws->row || !ws->type || !ws->eff_off || (ws->n_eff && (!ws->eff_meta || !ws->p0 || !ws->p1))) return false;
+  if (ws->var_off && ws->n_var && !ws->var_data) return false;
+  for (uint64_t i = 0; i < ws->n_ws; ++i)
+    if (ws->row[i] >= n_reads || ws->eff_off[i] > ws->eff_off[i + 1] || ws->eff_off[i + 1] > ws->n_eff) return false;
+  if (ws->var_off)
+    for (uint64_t p = 0; p < ws->n_eff; ++p)
+      if (ws->var_off[p] > ws->var_off[p + 1] || ws->var_off[p + 1] > ws->n_var) return false;
+  return true;
+}
+
+// am_vnode_read_host, then materialize_eager/3 of the write set's rows (ws null: the plain read)
+int vnode_read(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, am_read_result *hr,
+               const am_writeset *ws) {
   if (!v) return AM_ERR_INVALID;
   AM_LOCK(v->ctx);
   if (!v || !hb || !hr || !hb->key || !hb->type || !hb->read_vc || !hb->read_pres) return AM_ERR_INVALID;
   AM_HIP(hipSetDevice(v->ctx->device));
   const uint64_t n = hb->n_reads, nd = v->n_dc;
   if (n == 0) return AM_OK;
+  if (!ws_valid(ws, n)) {
+    am_set_error("am_read_objects_ws: a write-set row or offset lies outside the batch");
+    return AM_ERR_INVALID;
+  }
+  if (ws && ws->n_ws == 0) ws = nullptr;
   // occurrence rank of every read among the reads of its key: round j serves rank j
   std::vector<uint32_t> occ(n);
   {
@@ -524,7 +584,7 @@ int am_vnode_read_host(am_vnode *v, const am_read_batch *hb, const uint8_t *shou
     for (uint64_t j = 0; j < n; ++j) occ[idx[j]] = (j && hb->key[idx[j]] == hb->key[idx[j - 1]]) ? occ[idx[j - 1]] + 1 : 0;
   }
   const uint32_t rounds = 1 + *std::max_element(occ.begin(), occ.end());
-  if (rounds == 1) return read_round(v, hb, should_gc, hr);
+  if (rounds == 1) return read_round(v, hb, should_gc, hr, ws);
   for (uint32_t j = 0; j < rounds; ++j) {
     std::vector<uint64_t> sel;
     for (uint64_t i = 0; i < n; ++i)
@@ -557,7 +617,13 @@ int am_vnode_read_host(am_vnode *v, const am_read_batch *hb, const uint8_t *shou
     res.set_off = so;
     res.set_a.assign(so[m] + 1, 0), res.set_b.assign(so[m] + 1, 0);
     res.r.value.set_off = res.set_off.data(), res.r.value.set_a = res.set_a.data(), res.r.value.set_b = res.set_b.data();
-    int rc = read_round(v, &b, sg.data(), &res.r);
+    int rc;
+    if (ws) {
+      WsRound wr(*ws, sel);
+      rc = read_round(v, &b, sg.data(), &res.r, &wr.ws);
+    } else {
+      rc = read_round(v, &b, sg.data(), &res.r);
+    }
     if (rc) return rc;
     for (uint64_t q = 0; q < m; ++q) {  // scatter to the caller's columns
       const uint64_t i = sel[q];
@@ -578,6 +644,14 @@ int am_vnode_read_host(am_vnode *v, const am_read_batch *hb, const uint8_t *shou
     }
   }
   return AM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int am_vnode_read_host(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, am_read_result *hr) {
+  return vnode_read(v, hb, should_gc, hr, nullptr);
 }
 
 int am_vnode_relabel(am_vnode *v, const uint64_t *old_labels, const uint64_t *new_labels, uint64_t n) {
@@ -650,15 +724,27 @@ extern "C" {
 
 int am_read_objects_host(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
                          const am_read_batch *hb, am_read_result *hr) {
-  std::vector<uint64_t> key;
-  if (int rc = objects_keys(v, n_parts, part_key_base, part, hb, key)) return rc;
-  am_read_batch b = *hb;
-  b.key = key.data();
-  return am_vnode_read_host(v, &b, nullptr, hr);
+  return am_read_objects_ws_host(v, n_parts, part_key_base, part, hb, nullptr, hr);
 }
 
 int am_read_objects_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
                            const am_read_batch *hb, am_read_result *hr, am_ticket **out) {
+  return am_read_objects_ws_submit(v, n_parts, part_key_base, part, hb, nullptr, hr, out);
+}
+
+// the same with the reading transaction's own effects folded into the rows the write set names
+// (ws null or empty: the plain read)
+int am_read_objects_ws_host(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
+                            const am_read_batch *hb, const am_writeset *ws, am_read_result *hr) {
+  std::vector<uint64_t> key;
+  if (int rc = objects_keys(v, n_parts, part_key_base, part, hb, key)) return rc;
+  am_read_batch b = *hb;
+  b.key = key.data();
+  return vnode_read(v, &b, nullptr, hr, ws);
+}
+
+int am_read_objects_ws_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
+                              const am_read_batch *hb, const am_writeset *ws, am_read_result *hr, am_ticket **out) {
   if (!out) return AM_ERR_INVALID;
   am_ticket *t = new am_ticket();
   if (int rc = objects_keys(v, n_parts, part_key_base, part, hb, t->key)) {
@@ -668,8 +754,8 @@ int am_read_objects_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_k
   t->b = *hb;
   t->b.key = t->key.data();
   v->in_flight.fetch_add(1);
-  t->th = std::thread([t, v, hr]() {
-    t->rc = am_vnode_read_host(v, &t->b, nullptr, hr);
+  t->th = std::thread([t, v, hr, ws]() {
+    t->rc = vnode_read(v, &t->b, nullptr, hr, ws);
     v->in_flight.fetch_sub(1);
   });
   *out = t;

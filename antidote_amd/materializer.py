@@ -19,7 +19,7 @@ import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from . import abi
-from .oplog import HostBatch, HostLog, Op, Read
+from .oplog import HostBatch, HostLog, Op, Read, WriteSet
 
 IGNORE = None
 
@@ -523,6 +523,39 @@ class Materializer:
             return hb.result(0)
         finally:
             st.close()
+
+    def materialize_eager(self, n_dc: int, entries: Sequence[Tuple[int, Any, Sequence[Any]]],
+                          set_capacity: Optional[Sequence[int]] = None,
+                          in_status: Optional[Sequence[int]] = None) -> HostBatch:
+        """materializer:materialize_eager/3 (src/materializer.erl:62-70) for a batch (host memory in
+        and out, am_materialize_eager_host).  entries: [(Type, Snapshot, [Effect])], the snapshot as
+        Read.base_value takes it (None = Type:new()), the effects oldest first as encode_effect
+        takes them ("bad": an effect Type:update/2 raises on).  in_status: per entry, a failed
+        snapshot read's status to pass through.  Returns a HostBatch whose status[i] / value(i)
+        are entry i's outcome."""
+        ws = WriteSet([(i, t, effs) for i, (t, _, effs) in enumerate(entries)])
+        return self.materialize_eager_rows(n_dc, [(t, base) for t, base, _ in entries], ws, set_capacity, in_status)
+
+    def materialize_eager_rows(self, n_dc: int, values: Sequence[Tuple[int, Any]], ws: WriteSet,
+                               set_capacity: Optional[Sequence[int]] = None,
+                               in_status: Optional[Sequence[int]] = None) -> HostBatch:
+        """The same over a value batch [(Type, Snapshot)] and a WriteSet whose entries name rows
+        of it (am_writeset.row); in_status per row of the value batch.  Entry i of the returned
+        HostBatch is write-set entry i's outcome."""
+        import numpy as np
+        hin = HostBatch(n_dc, [Read(i, t, {}, base_value=base) for i, (t, base) in enumerate(values)])
+        hout = HostBatch(n_dc, [Read(i, t, {}) for i, (_, t, _) in enumerate(ws.entries)], set_capacity)
+        if not ws.entries:
+            return hout
+        b, _ = hin.structs()
+        _, r = hout.structs()
+        w = ws.as_struct()
+        ist = np.ascontiguousarray(in_status, np.int32) if in_status is not None else None
+        abi.check(self.L.am_materialize_eager_host(self.ctx, n_dc, ctypes.byref(w), ctypes.byref(b.base),
+                                                   ist.ctypes.data if ist is not None else None,
+                                                   ctypes.byref(r.value), hout.status.ctypes.data),
+                  "am_materialize_eager_host")
+        return hout
 
     def __del__(self):
         try:

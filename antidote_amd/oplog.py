@@ -322,3 +322,57 @@ class HostBatch:
                                                    if (int(self.last_ct_pres[i]) >> d) & 1}
         return ("ok", self.value(i), int(self.new_last_op[i]), ct, bool(self.is_new_ss[i]), int(self.count[i]),
                 int(self.flags[i]))
+
+
+class WriteSet:
+    """am_writeset in host memory: the reading transactions' own effects for some rows of a value
+    batch (reverse_and_filter_updates_per_key/2's output per key, src/clocksi_vnode.erl:660-668).
+
+    entries: [(row, type, [effect, ...])], each effect list in application order (oldest first),
+    effects shaped as encode_effect takes them; an effect given as the string "bad" is one
+    Type:update/2 raises on (AM_META_BAD)."""
+
+    def __init__(self, entries: Sequence[Tuple[int, int, Sequence[Any]]]):
+        self.entries = [(int(r), int(t), list(e)) for r, t, e in entries]
+        n = len(self.entries)
+        self.n_ws = n
+        self.row = np.asarray([r for r, _, _ in self.entries] or [0], U64)
+        self.type = np.asarray([t for _, t, _ in self.entries] or [0], np.uint8)
+        self.eff_off = np.zeros(n + 1, U64)
+        meta: List[int] = []
+        p0: List[int] = []
+        p1: List[int] = []
+        var: List[int] = []
+        var_off = [0]
+        for i, (_, t, effs) in enumerate(self.entries):
+            for eff in effs:
+                bad = isinstance(eff, str) and eff == "bad"
+                kind, a, b, words = (0, 0, 0, []) if bad else encode_effect(t, eff)
+                meta.append(abi.make_meta(0, kind, bad))
+                p0.append(a & 0xFFFFFFFFFFFFFFFF)
+                p1.append(b & 0xFFFFFFFFFFFFFFFF)
+                var += [w & 0xFFFFFFFFFFFFFFFF for w in words]
+                var_off.append(len(var))
+            self.eff_off[i + 1] = len(meta)
+        self.n_eff, self.n_var = len(meta), len(var)
+        self.eff_meta = np.asarray(meta or [0], np.uint8)
+        self.p0 = np.asarray(p0 or [0], U64)
+        self.p1 = np.asarray(p1 or [0], U64)
+        self.var_off = np.asarray(var_off, U64)
+        self.var_data = np.asarray(var or [0], U64)
+
+    def as_struct(self) -> abi.am_writeset:
+        s = abi.am_writeset()
+        s.n_ws, s.n_eff, s.n_var = self.n_ws, self.n_eff, self.n_var
+        p = lambda a: a.ctypes.data  # noqa: E731
+        s.row, s.type, s.eff_off, s.eff_meta = p(self.row), p(self.type), p(self.eff_off), p(self.eff_meta)
+        s.p0, s.p1, s.var_off, s.var_data = p(self.p0), p(self.p1), p(self.var_off), p(self.var_data)
+        self._struct = s
+        return s
+
+    def effect(self, i: int, j: int) -> Tuple[int, int, int, List[int]]:
+        """Effect j of entry i decoded from the columns: (meta, p0, p1, var words)."""
+        q = int(self.eff_off[i]) + j
+        return (int(self.eff_meta[q]), int(self.p0[q]), int(self.p1[q]),
+                [int(w) for w in self.var_data[int(self.var_off[q]):int(self.var_off[q + 1])]])
+

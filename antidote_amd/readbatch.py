@@ -23,7 +23,7 @@ import numpy as np
 
 from . import abi
 from .materializer import Materializer, Vnode
-from .oplog import HostBatch, Op, Read
+from .oplog import HostBatch, Op, Read, WriteSet
 
 
 class PendingRead:
@@ -84,8 +84,12 @@ class PartitionedReader:
         return abi.lib().am_key_partition(key, self.n_partitions)
 
     def submit(self, objects: Sequence[Tuple[int, int]], snapshot_time: Dict[int, int],
-               txid: Optional[int] = None, set_capacity: int = 4096) -> PendingRead:
-        """read_objects for one transaction, asynchronously: [(Key, Type)] at one snapshot."""
+               txid: Optional[int] = None, set_capacity: int = 4096,
+               write_set: Optional[Dict[int, Sequence]] = None) -> PendingRead:
+        """read_objects for one transaction, asynchronously: [(Key, Type)] at one snapshot.
+        write_set: {Key: [effects, oldest first]}, the transaction's own updates -- every request
+        of such a key returns materialize_eager(Type, Snapshot, effects) as its value
+        (apply_tx_updates_to_snapshot/4), folded on the device (am_read_objects_ws_submit)."""
         parts = np.zeros(max(len(objects), 1), np.uint32)
         reads = []
         for i, (key, type_) in enumerate(objects):
@@ -97,18 +101,29 @@ class PartitionedReader:
         hb = HostBatch(self.n_dc, reads, [set_capacity] * len(reads))
         b, r = hb.structs()
         t = ctypes.c_void_p()
-        abi.check(self.mat.L.am_read_objects_submit(self.vnode.handle, self.n_partitions, self.part_key_base.ctypes.data,
-                                                    parts.ctypes.data, ctypes.byref(b), ctypes.byref(r),
-                                                    ctypes.byref(t)), "am_read_objects_submit")
-        pr = PendingRead(t, hb, (b, r, parts), owner=self)
+        ws = w = None
+        if write_set:
+            ws = WriteSet([(i, type_, write_set[key]) for i, (key, type_) in enumerate(objects) if write_set.get(key)])
+            w = ws.as_struct()
+        if w is not None:
+            abi.check(self.mat.L.am_read_objects_ws_submit(self.vnode.handle, self.n_partitions,
+                                                           self.part_key_base.ctypes.data, parts.ctypes.data,
+                                                           ctypes.byref(b), ctypes.byref(w), ctypes.byref(r),
+                                                           ctypes.byref(t)), "am_read_objects_ws_submit")
+        else:
+            abi.check(self.mat.L.am_read_objects_submit(self.vnode.handle, self.n_partitions,
+                                                        self.part_key_base.ctypes.data, parts.ctypes.data,
+                                                        ctypes.byref(b), ctypes.byref(r), ctypes.byref(t)),
+                      "am_read_objects_submit")
+        pr = PendingRead(t, hb, (b, r, parts, ws, w), owner=self)
         self._pending.add(pr)
         return pr
 
     def read_objects(self, objects: Sequence[Tuple[int, int]], snapshot_time: Dict[int, int],
-                     txid: Optional[int] = None) -> list:
+                     txid: Optional[int] = None, write_set: Optional[Dict[int, Sequence]] = None) -> list:
         """Per object ('ok', Value, NewLastOp, LastOpCt, IsNewSS, Count, flags) or
         ('error', status) -- AM_ERR_COLD_PATH when the read needs the log -- in request order."""
-        return self.submit(objects, snapshot_time, txid).result()
+        return self.submit(objects, snapshot_time, txid, write_set=write_set).result()
 
     def close(self):
         for pr in list(self._pending):

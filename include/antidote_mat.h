@@ -40,6 +40,13 @@
  *   am_read_objects_submit  clocksi_interactive_coord's read_objects fan-out over a GPU's
  *                           partitions (src/clocksi_interactive_coord.erl:732-747,
  *                           src/clocksi_readitem_server.erl:217-228) as one async batch
+ *   am_materialize_eager    clocksi_materializer:materialize_eager/3 (src/clocksi_materializer.erl:
+ *                           272-274, src/materializer.erl:62-70), batched: a snapshot plus the
+ *                           reading transaction's own effects, as clocksi_vnode:read_data_item/5
+ *                           (src/clocksi_vnode.erl:99-107) and clocksi_downstream:
+ *                           generate_downstream_op/6 (src/clocksi_downstream.erl:41-68) call it
+ *   am_read_objects_ws_*    the read_objects fan-out with apply_tx_updates_to_snapshot/4
+ *                           (src/clocksi_interactive_coord.erl:486-507, 883-894) on the device
  *   am_key_partition        log_utilities:get_key_partition/1 + convert_key/1: integer
  *   am_key_partition_bytes  keys, binaries (list_to_integer text or SHA-1 chash_key) and
  *                           other terms (src/log_utilities.erl:60-79,100-118)
@@ -72,7 +79,7 @@
 extern "C" {
 #endif
 
-#define AM_ABI_VERSION 14
+#define AM_ABI_VERSION 15
 #define AM_MAX_DC 32
 
 /* CRDT types (the reference's type atoms) */
@@ -557,6 +564,81 @@ int am_read_objects_host(am_vnode *v, uint32_t n_parts, const uint64_t *part_key
 int am_read_objects_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
                            const am_read_batch *host_batch, am_read_result *host_res, am_ticket **out);
 int am_ticket_wait(am_ticket *t);
+
+/* ---- read-your-writes: materialize_eager/3 on the device (am_eager.hip, ABI 15) ----
+ * materializer:materialize_eager(Type, Snapshot, Effects) (src/materializer.erl:62-70) folds a
+ * transaction's own effects for a key into the snapshot it read: no clocks, no inclusion test,
+ * no op log.  clocksi_vnode:read_data_item/5 (src/clocksi_vnode.erl:99-107) does it to every
+ * read of a key the transaction wrote, with the effects reverse_and_filter_updates_per_key/2
+ * (:660-668) returns; the coordinator does it to every read_objects reply
+ * (apply_tx_updates_to_snapshot/4, src/clocksi_interactive_coord.erl:883-894).
+ *
+ * The reading transactions' own effects, for n_ws rows of a value batch.  Effects use am_op_log's
+ * payload encoding (kind and AM_META_BAD in eff_meta, DC bits ignored; p0, p1; var words). */
+typedef struct am_writeset {
+  uint64_t n_ws, n_eff, n_var;
+  const uint64_t *row;      /* [n_ws] row in the input values / status, distinct            */
+  const uint8_t  *type;     /* [n_ws] am_type of that read                                  */
+  const uint64_t *eff_off;  /* [n_ws+1] entry i's effects, in APPLICATION order (oldest     */
+                            /* first: reverse_and_filter_updates_per_key's output)          */
+  const uint8_t  *eff_meta; /* [n_eff] */
+  const uint64_t *p0, *p1;  /* [n_eff] */
+  const uint64_t *var_off;  /* [n_eff+1] or NULL */
+  const uint64_t *var_data; /* [n_var] */
+} am_writeset;
+/* Limits of one entry's write set (add-wins set and MV register): the tokens its effects insert
+ * (births: every AW add token, one per MV assign), the tokens they drop (kills: every AW remove
+ * token, every MV overridden token) and its effects.  An entry beyond them gets AM_ERR_CAPACITY.
+ * The base value has no limit: it is streamed, never held on chip. */
+#define AM_EAGER_MAX_BIRTHS 1024u
+#define AM_EAGER_MAX_KILLS 2048u
+#define AM_EAGER_MAX_EFFECTS 32767u
+/* Base pairs streamed per pass by the two kernel shapes: one wavefront per entry whose write set
+ * has at most AM_EAGER_SMALL_WORDS effects + variable words (and, for a bounded counter, at most
+ * AM_EAGER_SMALL_SLOTS slots n_dc * n_dc + n_dc), else one 256-thread workgroup. */
+#define AM_EAGER_TILE_WAVE 64u
+#define AM_EAGER_TILE_WG 256u
+#define AM_EAGER_SMALL_WORDS 128u
+#define AM_EAGER_SMALL_SLOTS 128u
+/* Entry i of dev_out / out_status = materialize_eager(type[i], the value at row[i] of dev_in,
+ * entry i's effects).  dev_out has n_ws rows (its own set_off capacities); dev_in is not written
+ * (NULL members => the type's new() value).  Device pointers (the structs themselves live in
+ * host memory); asynchronous on the context stream, no host readback.
+ *   in_status[row[i]] != AM_OK      out_status[i] is a copy of it, the output row is empty: the
+ *                                   {error, Reason} pass-through of src/clocksi_vnode.erl:105-106
+ *   AM_ERR_UNEXPECTED_OPERATION     an effect carries AM_META_BAD or a malformed variable payload
+ *                                   (the store builder's rule); wins over every other code, as
+ *                                   the reference stops at the first bad effect
+ *   AM_ERR_OVERFLOW                 a PN / bounded-counter result outside int64 (summed exactly
+ *                                   in 128 bits)
+ *   AM_ERR_CAPACITY                 the result exceeds the row's set_off capacity, or the entry
+ *                                   the limits above
+ *   AM_ERR_INVALID                  an unknown type, effect offsets outside the write set, or a
+ *                                   set / bounded-counter entry without set columns in dev_out
+ * A row with an error status holds no value (set_len 0).
+ * Per type (the reference's Type:update/2): PN the sum; LWW erlang:max(Effect, State); bounded
+ * counter the keyed sums of the P / D slots, a slot present once an effect touched it; add-wins
+ * set and MV register the closed form of am_sets.hip with the base pairs as births before the
+ * first effect -- a birth survives unless a kill of the same token (set: and element) comes at a
+ * strictly later effect.  Set order: elements ascending, within one element the newest effect's
+ * add tokens first (in the effect's order), the base tokens last in base order; MV order:
+ * (value, token), equal pairs once.  As in am_sets.hip the closed form differs from the list
+ * semantics only when a live token is added again (both copies are kept). */
+int am_materialize_eager(am_ctx *ctx, uint32_t n_dc, const am_writeset *dev_ws, const am_values *dev_in,
+                         const int32_t *in_status /* or NULL */, am_values *dev_out, int32_t *out_status);
+/* The same with host pointers; blocks.  Only the rows named by host_ws->row are read. */
+int am_materialize_eager_host(am_ctx *ctx, uint32_t n_dc, const am_writeset *host_ws, const am_values *host_in,
+                              const int32_t *in_status /* or NULL */, am_values *host_out, int32_t *out_status);
+/* am_read_objects_host / _submit, then the value and status of the requests host_ws->row names
+ * are replaced by the eager result (capacity: host_res's own set_off), on the device before the
+ * result is copied back; every other result column stays the snapshot read's.  host_ws == NULL
+ * or n_ws == 0: exactly am_read_objects_host / _submit.  host_ws and its arrays must stay valid
+ * until the call (the ticket's wait) returns. */
+int am_read_objects_ws_host(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
+                            const am_read_batch *host_batch, const am_writeset *host_ws, am_read_result *host_res);
+int am_read_objects_ws_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
+                              const am_read_batch *host_batch, const am_writeset *host_ws, am_read_result *host_res,
+                              am_ticket **out);
 
 /* ---- op-cache ingestion + garbage collection ----
  * Builds a new store from `st` (st is unchanged; destroy it when no read uses it):
