@@ -33,6 +33,7 @@ AM_ERR_CORRUPTED_OPS_CACHE = 1
 AM_ERR_UNEXPECTED_OPERATION = 2
 AM_ERR_OVERFLOW = 3
 AM_ERR_CAPACITY = 4
+AM_ERR_NO_PERMISSIONS = 6  # {error, no_permissions} (am_generate_downstream)
 AM_ERR_INVALID = -1
 AM_ERR_UNSUPPORTED = -5
 AM_FLAG_MISSING_DC_LOGGED = 0x1
@@ -97,6 +98,22 @@ class am_writeset(ctypes.Structure):
     ]
 
 
+class am_updates(ctypes.Structure):
+    _fields_ = [
+        ("n_up", c_uint64), ("n_var", c_uint64),
+        ("row", c_void_p), ("type", c_void_p), ("op", c_void_p), ("a0", c_void_p), ("a1", c_void_p),
+        ("var_off", c_void_p), ("var_data", c_void_p),
+    ]
+
+
+class am_effects(ctypes.Structure):
+    _fields_ = [
+        ("var_cap", c_uint64),
+        ("eff_off", c_void_p), ("eff_meta", c_void_p), ("p0", c_void_p), ("p1", c_void_p),
+        ("var_off", c_void_p), ("var_data", c_void_p), ("n_var", c_void_p), ("avail", c_void_p),
+    ]
+
+
 class am_synth_params(ctypes.Structure):
     _fields_ = [
         ("seed", c_uint64), ("n_keys", c_uint64), ("ops_per_key", c_uint32), ("n_dc", c_uint32),
@@ -128,6 +145,13 @@ AM_OPS_THRESHOLD = 50
 AM_EAGER_MAX_BIRTHS, AM_EAGER_MAX_KILLS, AM_EAGER_MAX_EFFECTS = 1024, 2048, 32767
 AM_EAGER_TILE_WAVE, AM_EAGER_TILE_WG = 64, 256
 AM_EAGER_SMALL_WORDS, AM_EAGER_SMALL_SLOTS = 128, 128
+# am_generate_downstream: update op codes per type (AM_UP_*) and the workgroup fill's split
+AM_UP_PN_INCREMENT, AM_UP_PN_DECREMENT = 0, 1
+AM_UP_LWW_ASSIGN = 0
+AM_UP_AW_ADD, AM_UP_AW_REMOVE, AM_UP_AW_RESET = 0, 1, 2
+AM_UP_MV_ASSIGN, AM_UP_MV_RESET = 0, 1
+AM_UP_BC_INCREMENT, AM_UP_BC_DECREMENT, AM_UP_BC_TRANSFER = 0, 1, 2
+AM_DS_TILE_WG = 256
 
 
 # (name, restype, argtypes) of every exported symbol declared in include/antidote_mat.h
@@ -203,6 +227,15 @@ SIGNATURES = [
                                         POINTER(am_writeset), POINTER(am_read_result)]),
     ("am_read_objects_ws_submit", c_int, [c_void_p, c_uint32, c_void_p, c_void_p, POINTER(am_read_batch),
                                           POINTER(am_writeset), POINTER(am_read_result), POINTER(c_void_p)]),
+    ("am_generate_downstream", c_int, [c_void_p, c_uint32, POINTER(am_updates), POINTER(am_values), c_void_p,
+                                       POINTER(am_effects), c_void_p]),
+    ("am_generate_downstream_host", c_int, [c_void_p, c_uint32, POINTER(am_updates), POINTER(am_values), c_void_p,
+                                            POINTER(am_effects), c_void_p]),
+    ("am_update_objects_host", c_int, [c_void_p, c_uint32, c_void_p, c_void_p, POINTER(am_read_batch), c_void_p,
+                                       POINTER(am_writeset), POINTER(am_updates), POINTER(am_effects), c_void_p]),
+    ("am_update_objects_submit", c_int, [c_void_p, c_uint32, c_void_p, c_void_p, POINTER(am_read_batch), c_void_p,
+                                         POINTER(am_writeset), POINTER(am_updates), POINTER(am_effects), c_void_p,
+                                         POINTER(c_void_p)]),
     ("am_codec_create", c_int, [POINTER(c_void_p)]),
     ("am_codec_destroy", c_int, [c_void_p]),
     ("am_codec_intern", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),

@@ -502,37 +502,11 @@ int launch_eager(am_ctx *ctx, uint32_t nd, const am_writeset *ws, const am_value
   return AM_OK;
 }
 
-// host arrays -> one device arena (stream-ordered copies); the host sources outlive the call
-struct Stage {
-  struct Item {
-    const void *h;
-    size_t bytes, off;
-  };
-  std::vector<Item> items;
-  size_t total = 0;
-  size_t add(const void *h, size_t bytes) {
-    items.push_back({h, bytes, total});
-    total += (bytes + 255) & ~(size_t)255;
-    return items.size() - 1;
-  }
-  char *arena = nullptr;
-  int upload(am_ctx *c) {
-    if (int rc = am_dev_alloc(c, total ? total : 256, (void **)&arena)) return rc;
-    for (const Item &it : items)
-      if (it.h && it.bytes) AM_HIP(hipMemcpyAsync(arena + it.off, it.h, it.bytes, hipMemcpyHostToDevice, c->stream));
-    return AM_OK;
-  }
-  template <class T>
-  T *dev(size_t item) const {
-    return (T *)(arena + items[item].off);
-  }
-};
-
 // the device copy of a host write set inside a staged arena
 struct WsStage {
   size_t row, type, eff_off, meta, p0, p1, var_off, var_data;
   bool has_var;
-  void add(Stage &st, const am_writeset *h) {
+  void add(am_stage &st, const am_writeset *h) {
     const uint64_t n = h->n_ws, ne = h->n_eff;
     has_var = h->var_off != nullptr;
     row = st.add(h->row, n * 8), type = st.add(h->type, n), eff_off = st.add(h->eff_off, (n + 1) * 8);
@@ -540,7 +514,7 @@ struct WsStage {
     var_off = st.add(h->var_off, has_var ? (ne + 1) * 8 : 0);
     var_data = st.add(h->var_data, has_var ? h->n_var * 8 : 0);
   }
-  am_writeset dev(const Stage &st, const am_writeset *h) const {
+  am_writeset dev(const am_stage &st, const am_writeset *h) const {
     am_writeset d = *h;
     d.row = st.dev<uint64_t>(row), d.type = st.dev<uint8_t>(type), d.eff_off = st.dev<uint64_t>(eff_off);
     d.eff_meta = st.dev<uint8_t>(meta), d.p0 = st.dev<uint64_t>(p0), d.p1 = st.dev<uint64_t>(p1);
@@ -599,7 +573,7 @@ extern "C" int am_materialize_eager_host(am_ctx *ctx, uint32_t n_dc, const am_wr
   am_writeset hw2 = *hw;
   hw2.row = rows.data();
   const uint64_t ocap = hout->set_off ? hout->set_off[n] : 0;
-  Stage st;
+  am_stage st;
   WsStage wss;
   wss.add(st, &hw2);
   const size_t i_st = st.add(ist.data(), n * 4), i_v0 = st.add(v0.data(), n * 8), i_v1 = st.add(v1.data(), n * 8);
@@ -659,7 +633,7 @@ int am_eager_apply_result(am_ctx *ctx, uint32_t n_dc, const am_writeset *hw, con
   std::vector<uint64_t> so(n + 1, 0);
   for (uint64_t i = 0; i < n; ++i)
     so[i + 1] = so[i] + (sets ? host_set_off[hw->row[i] + 1] - host_set_off[hw->row[i]] : 0);
-  Stage st;
+  am_stage st;
   WsStage wss;
   wss.add(st, hw);
   const size_t t_so = st.add(so.data(), (n + 1) * 8), t_st = st.add(nullptr, n * 4), t_v0 = st.add(nullptr, n * 8);

@@ -23,10 +23,12 @@ struct Arena {
 }  // namespace
 
 // Stages a host batch into one device arena, runs `run` on the device batch/result and
-// copies the result columns back.
+// copies the result columns back.  values_on_device: every value column gets device room
+// (capacities from hr->value.set_off) whether or not hr has a host array for it, and NO result
+// column is copied back -- `run` consumes the result on the device (am_update_objects_*).
 static int run_host(am_ctx *c, const am_store *st, const am_read_batch *hb, am_read_result *hr,
                     const std::function<int(const am_read_batch *, am_read_result *, const void *)> &run,
-                    const void *extra_host = nullptr, size_t extra_bytes = 0) {
+                    const void *extra_host = nullptr, size_t extra_bytes = 0, bool values_on_device = false) {
   if (!c || !st || !hb || !hr || !hb->key || !hb->type || !hb->read_vc || !hb->read_pres) return AM_ERR_INVALID;
   const uint64_t n = hb->n_reads;
   if (n == 0) return AM_OK;
@@ -41,7 +43,7 @@ static int run_host(am_ctx *c, const am_store *st, const am_read_batch *hb, am_r
     const void **dptr;
   };
   struct Out {
-    void *h;
+    void *h;  // null: device room only
     size_t bytes;
     void **dptr;
   };
@@ -53,7 +55,7 @@ static int run_host(am_ctx *c, const am_store *st, const am_read_batch *hb, am_r
     if (h) ins.push_back({h, bytes, slot});
   };
   auto out = [&](void *h, size_t bytes, void **slot) {
-    if (h) outs.push_back({h, bytes, slot});
+    if (h) outs.push_back({values_on_device ? nullptr : h, bytes, slot});
   };
   in(hb->key, n * 8, (const void **)&db.key);
   in(hb->type, n, (const void **)&db.type);
@@ -84,12 +86,16 @@ static int run_host(am_ctx *c, const am_store *st, const am_read_batch *hb, am_r
   out(hr->is_new_ss, n, (void **)&dr.is_new_ss);
   out(hr->count, n * 4, (void **)&dr.count);
   out(hr->flags, n, (void **)&dr.flags);
-  out(hr->value.v0, n * 8, (void **)&dr.value.v0);
-  out(hr->value.v1, n * 8, (void **)&dr.value.v1);
-  out(hr->value.vflag, n, (void **)&dr.value.vflag);
-  out(hr->value.set_len, n * 4, (void **)&dr.value.set_len);
-  out(hr->value.set_a, nset_out * 8, (void **)&dr.value.set_a);
-  out(hr->value.set_b, nset_out * 8, (void **)&dr.value.set_b);
+  auto val = [&](void *h, size_t bytes, void **slot) {
+    if (values_on_device) outs.push_back({nullptr, bytes, slot});
+    else out(h, bytes, slot);
+  };
+  val(hr->value.v0, n * 8, (void **)&dr.value.v0);
+  val(hr->value.v1, n * 8, (void **)&dr.value.v1);
+  val(hr->value.vflag, n, (void **)&dr.value.vflag);
+  val(hr->value.set_len, n * 4, (void **)&dr.value.set_len);
+  val(hr->value.set_a, nset_out * 8, (void **)&dr.value.set_a);
+  val(hr->value.set_b, nset_out * 8, (void **)&dr.value.set_b);
   if (!hr->status || !hr->new_last_op || !hr->last_ct || !hr->last_ct_pres || !hr->last_ct_ignore || !hr->is_new_ss ||
       !hr->count || !hr->flags) {
     am_set_error("host batch: every result column is required");
@@ -122,7 +128,7 @@ static int run_host(am_ctx *c, const am_store *st, const am_read_batch *hb, am_r
   if (e == hipSuccess) {
     rc = run(&db, &dr, extra_dev);
     for (size_t i = 0; i < outs.size() && e == hipSuccess && !rc; ++i)
-      e = hipMemcpyAsync(outs[i].h, arena + out_off[i], outs[i].bytes, hipMemcpyDeviceToHost, c->stream);
+      if (outs[i].h) e = hipMemcpyAsync(outs[i].h, arena + out_off[i], outs[i].bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
   am_dev_release(c, arena);  // stream-ordered reuse by the next host batch
@@ -156,9 +162,9 @@ extern "C" int am_snapcache_read_host(am_ctx *c, am_snapcache *sc, const am_stor
 int am_run_host_batch(am_ctx *c, const am_store *st, const am_read_batch *hb, am_read_result *hr,
                       const void *extra_host, size_t extra_bytes,
                       int (*run)(void *arg, const am_read_batch *db, am_read_result *dr, const void *extra_dev),
-                      void *arg) {
+                      void *arg, bool values_on_device) {
   return run_host(
       c, st, hb, hr,
       [&](const am_read_batch *db, am_read_result *dr, const void *extra_dev) { return run(arg, db, dr, extra_dev); },
-      extra_host, extra_bytes);
+      extra_host, extra_bytes, values_on_device);
 }

@@ -13,7 +13,7 @@
 
 #include "../../include/antidote_mat.h"
 
-enum { AM_SCR_PLAN = 0, AM_SCR_BIGMETA = 1, AM_SCR_BIGREC = 2, AM_SCR_ROWS = 3, AM_SCR_GRP = 4, AM_SCR_SPARE = 5, AM_SCR_SNAP = 6, AM_SCR_GC = 7, AM_SCR_SIZES = 8, AM_SCR_MISC = 9, AM_SCR_INCL = 10, AM_SCR_ROUTE = 11, AM_SCR_EAGER = 12, AM_N_SCR = 13 };
+enum { AM_SCR_PLAN = 0, AM_SCR_BIGMETA = 1, AM_SCR_BIGREC = 2, AM_SCR_ROWS = 3, AM_SCR_GRP = 4, AM_SCR_SPARE = 5, AM_SCR_SNAP = 6, AM_SCR_GC = 7, AM_SCR_SIZES = 8, AM_SCR_MISC = 9, AM_SCR_INCL = 10, AM_SCR_ROUTE = 11, AM_SCR_EAGER = 12, AM_SCR_DOWN = 13, AM_N_SCR = 14 };
 
 struct am_ctx {
   int device = 0;
@@ -231,6 +231,38 @@ int am_store_key_lens(am_ctx *c, const am_store *st, uint64_t m, const uint64_t 
 // are replaced by the eager result, on the context stream.  am_vnode.hip's read_objects path.
 int am_eager_apply_result(am_ctx *ctx, uint32_t n_dc, const am_writeset *host_ws, const uint64_t *host_set_off,
                           am_read_result *dr);
+
+// generate_downstream_op/6 over a device result (am_downstream.hip): the effects of host updates
+// naming rows of dr (n_rows of them), generated from dr's values and statuses on the context
+// stream; only the effects, statuses and avail are copied to the host.  am_update_objects_*.
+int am_downstream_apply_result(am_ctx *ctx, uint32_t n_dc, uint64_t n_rows, const am_updates *host_up,
+                               const am_read_result *dr, am_effects *host_eff, int32_t *out_status);
+
+// host arrays -> one device arena (stream-ordered copies); the host sources outlive the call
+struct am_stage {
+  struct Item {
+    const void *h;
+    size_t bytes, off;
+  };
+  std::vector<Item> items;
+  size_t total = 0;
+  size_t add(const void *h, size_t bytes) {
+    items.push_back({h, bytes, total});
+    total += (bytes + 255) & ~(size_t)255;
+    return items.size() - 1;
+  }
+  char *arena = nullptr;
+  int upload(am_ctx *c) {
+    if (int rc = am_dev_alloc(c, total ? total : 256, (void **)&arena)) return rc;
+    for (const Item &it : items)
+      if (it.h && it.bytes) AM_HIP(hipMemcpyAsync(arena + it.off, it.h, it.bytes, hipMemcpyHostToDevice, c->stream));
+    return AM_OK;
+  }
+  template <class T>
+  T *dev(size_t item) const {
+    return (T *)(arena + items[item].off);
+  }
+};
 
 // Short-read tier (am_rows.hip): reads with at most short_max ops (and error reads) are
 // materialized by one 16-lane row each.  list/count (set types only): reads the tier

@@ -25,7 +25,7 @@
 int am_run_host_batch(am_ctx *c, const am_store *st, const am_read_batch *hb, am_read_result *hr,
                       const void *extra_host, size_t extra_bytes,
                       int (*run)(void *arg, const am_read_batch *db, am_read_result *dr, const void *extra_dev),
-                      void *arg);  // am_host.hip
+                      void *arg, bool values_on_device = false);  // am_host.hip
 
 namespace {
 
@@ -201,10 +201,18 @@ int grow_keys(am_vnode *v, uint64_t new_n) {
   return AM_OK;
 }
 
+// generate_downstream_op/6 on the values a read leaves on the device (am_update_objects_*)
+struct DownArg {
+  const am_updates *up;  // host; rows of the batch
+  am_effects *eff;       // host
+  int32_t *out_status;   // host [n_up]
+};
 struct ReadArg {
   am_vnode *v;
   const am_writeset *ws;       // the reading transaction's own effects (host; rows of this round), or null
   const uint64_t *host_set_off;  // the result's set capacities (host copy)
+  const DownArg *down;         // the updates to turn into effects, or null
+  uint64_t n_reads;
 };
 int run_round(void *arg, const am_read_batch *db, am_read_result *dr, const void *extra_dev) {
   const ReadArg *a = static_cast<ReadArg *>(arg);
@@ -213,17 +221,20 @@ int run_round(void *arg, const am_read_batch *db, am_read_result *dr, const void
                                 v->thr_pres);
   // apply_tx_updates_to_snapshot/4 on the device result, before it is copied back
   if (!rc && a->ws && a->ws->n_ws) rc = am_eager_apply_result(v->ctx, v->n_dc, a->ws, a->host_set_off, dr);
+  // ... and Type:downstream/2 on the values, which stay on the device
+  if (!rc && a->down)
+    rc = am_downstream_apply_result(v->ctx, v->n_dc, a->n_reads, a->down->up, dr, a->down->eff, a->down->out_status);
   return rc;
 }
 
 // one round of reads over distinct keys (host arrays), then the GCs they triggered
 int read_round(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, am_read_result *hr,
-               const am_writeset *ws = nullptr) {
-  ReadArg a{v, ws, hr->value.set_off};
+               const am_writeset *ws = nullptr, const DownArg *down = nullptr) {
   const uint64_t n = hb->n_reads;
+  ReadArg a{v, ws, hr->value.set_off, down, n};
   std::vector<uint8_t> sg(n, 0);
   if (should_gc) std::copy(should_gc, should_gc + n, sg.begin());
-  int rc = am_run_host_batch(v->ctx, v->st, hb, hr, sg.data(), sg.size(), run_round, &a);
+  int rc = am_run_host_batch(v->ctx, v->st, hb, hr, sg.data(), sg.size(), run_round, &a, down != nullptr);
   if (rc) return rc;
   // the GC mask of the batch's keys only (keys past the vnode's are invalid reads)
   std::vector<uint64_t> keys;
@@ -563,7 +574,7 @@ bool ws_valid(const am_writeset *ws, uint64_t n_reads) {
 
 // am_vnode_read_host, then materialize_eager/3 of the write set's rows (ws null: the plain read)
 int vnode_read(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, am_read_result *hr,
-               const am_writeset *ws) {
+               const am_writeset *ws, const DownArg *down = nullptr) {
   if (!v) return AM_ERR_INVALID;
   AM_LOCK(v->ctx);
   if (!v || !hb || !hr || !hb->key || !hb->type || !hb->read_vc || !hb->read_pres) return AM_ERR_INVALID;
@@ -584,7 +595,11 @@ int vnode_read(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, a
     for (uint64_t j = 0; j < n; ++j) occ[idx[j]] = (j && hb->key[idx[j]] == hb->key[idx[j - 1]]) ? occ[idx[j - 1]] + 1 : 0;
   }
   const uint32_t rounds = 1 + *std::max_element(occ.begin(), occ.end());
-  if (rounds == 1) return read_round(v, hb, should_gc, hr, ws);
+  if (down && rounds != 1) {
+    am_set_error("am_update_objects: the requests must name distinct keys");
+    return AM_ERR_INVALID;
+  }
+  if (rounds == 1) return read_round(v, hb, should_gc, hr, ws, down);
   for (uint32_t j = 0; j < rounds; ++j) {
     std::vector<uint64_t> sel;
     for (uint64_t i = 0; i < n; ++i)
@@ -756,6 +771,55 @@ int am_read_objects_ws_submit(am_vnode *v, uint32_t n_parts, const uint64_t *par
   v->in_flight.fetch_add(1);
   t->th = std::thread([t, v, hr, ws]() {
     t->rc = vnode_read(v, &t->b, nullptr, hr, ws);
+    v->in_flight.fetch_sub(1);
+  });
+  *out = t;
+  return AM_OK;
+}
+
+// read_objects with the whole result left on the device, then generate_downstream_op/6 on it: no
+// column of the read is copied back (res only supplies the set capacities), only the effects are
+static int update_objects(am_vnode *v, const am_read_batch *b, const uint64_t *set_off, const am_writeset *ws,
+                          const am_updates *up, am_effects *eff, int32_t *out_status) {
+  if (b->n_reads == 0) {  // no request: no update can name one
+    if (up->n_up || !eff->n_var || !eff->eff_off || !eff->var_off) return AM_ERR_INVALID;
+    *eff->n_var = 0, eff->eff_off[0] = 0, eff->var_off[0] = 0;
+    return AM_OK;
+  }
+  HostResult res(b->n_reads, v->n_dc, 0);
+  if (set_off) res.set_off.assign(set_off, set_off + b->n_reads + 1);
+  res.r.value.set_off = res.set_off.data();
+  res.r.value.v0 = nullptr, res.r.value.v1 = nullptr, res.r.value.vflag = nullptr;
+  res.r.value.set_len = nullptr, res.r.value.set_a = nullptr, res.r.value.set_b = nullptr;
+  DownArg d{up, eff, out_status};
+  return vnode_read(v, b, nullptr, &res.r, ws, &d);
+}
+
+int am_update_objects_host(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
+                           const am_read_batch *hb, const uint64_t *set_off, const am_writeset *ws, const am_updates *up,
+                           am_effects *eff, int32_t *out_status) {
+  if (!v || !up || !eff || !out_status) return AM_ERR_INVALID;
+  std::vector<uint64_t> key;
+  if (int rc = objects_keys(v, n_parts, part_key_base, part, hb, key)) return rc;
+  am_read_batch b = *hb;
+  b.key = key.data();
+  return update_objects(v, &b, set_off, ws, up, eff, out_status);
+}
+
+int am_update_objects_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
+                             const am_read_batch *hb, const uint64_t *set_off, const am_writeset *ws, const am_updates *up,
+                             am_effects *eff, int32_t *out_status, am_ticket **out) {
+  if (!v || !up || !eff || !out_status || !out) return AM_ERR_INVALID;
+  am_ticket *t = new am_ticket();
+  if (int rc = objects_keys(v, n_parts, part_key_base, part, hb, t->key)) {
+    delete t;
+    return rc;
+  }
+  t->b = *hb;
+  t->b.key = t->key.data();
+  v->in_flight.fetch_add(1);
+  t->th = std::thread([=]() {
+    t->rc = update_objects(v, &t->b, set_off, ws, up, eff, out_status);
     v->in_flight.fetch_sub(1);
   });
   *out = t;

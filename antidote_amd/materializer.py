@@ -19,7 +19,7 @@ import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from . import abi
-from .oplog import HostBatch, HostLog, Op, Read, WriteSet
+from .oplog import Effects, HostBatch, HostLog, Op, Read, Updates, WriteSet
 
 IGNORE = None
 
@@ -556,6 +556,67 @@ class Materializer:
                                                    ctypes.byref(r.value), hout.status.ctypes.data),
                   "am_materialize_eager_host")
         return hout
+
+    # ---- downstream generation (clocksi_downstream:generate_downstream_op/6) ----
+    @staticmethod
+    def downstream_capacity(hin: HostBatch, ups: Updates) -> int:
+        """An upper bound of the effects' variable words: per update the row's pairs (every token
+        once) plus a header per state element and per requested element, and the add tokens."""
+        cap = 0
+        for i, (r, _, _) in enumerate(ups.entries):
+            cap += 4 * int(hin.b_set_len[r]) + 4 * int(ups.var_off[i + 1] - ups.var_off[i])
+        return cap
+
+    def generate_downstream(self, n_dc: int, values: Sequence[Tuple[int, Any]], updates, tokens=None,
+                            in_status: Optional[Sequence[int]] = None, var_cap: Optional[int] = None):
+        """Type:downstream/2 for a batch on the device (am_generate_downstream_host).  values:
+        [(Type, Snapshot)] as materialize_eager_rows takes them; updates: [(row, type, update)]
+        (oplog.Updates' shapes, rows distinct) or an Updates; tokens: a callable returning fresh
+        interned tokens.  Returns ([effect | ('error', status)], avail[n_up], Effects)."""
+        import numpy as np
+        ups = updates if isinstance(updates, Updates) else Updates(updates, tokens)
+        hin = HostBatch(n_dc, [Read(i, t, {}, base_value=base) for i, (t, base) in enumerate(values)])
+        eff = Effects(ups, self.downstream_capacity(hin, ups) if var_cap is None else var_cap)
+        b, _ = hin.structs()
+        u, e = ups.as_struct(), eff.as_struct()
+        ist = np.ascontiguousarray(in_status, np.int32) if in_status is not None else None
+        abi.check(self.L.am_generate_downstream_host(self.ctx, n_dc, ctypes.byref(u), ctypes.byref(b.base),
+                                                     ist.ctypes.data if ist is not None else None, ctypes.byref(e),
+                                                     eff.status.ctypes.data), "am_generate_downstream_host")
+        return eff.effects(), [int(a) for a in eff.avail[:ups.n_up]], eff
+
+    def update_rounds(self, n_dc: int, values: Sequence[Tuple[int, Any]], tx_updates, tokens=None,
+                      set_capacity: int = 4096) -> list:
+        """A transaction's updates [(row, type, update)], repeated rows allowed, in order: the
+        reference generates them one after another, each seeing the write set so far
+        (src/clocksi_interactive_coord.erl:986).  Here round j takes every row's j-th update (rows
+        distinct within a round), and after each round that round's effects are folded into the
+        values with materialize_eager_rows.  Returns the effects in update order."""
+        vals = list(values)
+        seen: Dict[int, int] = {}
+        rounds: List[List[int]] = []
+        for q, (r, _, _) in enumerate(tx_updates):
+            j = seen.get(r, 0)
+            seen[r] = j + 1
+            if j == len(rounds):
+                rounds.append([])
+            rounds[j].append(q)
+        out: List[Any] = [None] * len(tx_updates)
+        for sel in rounds:
+            effs, _, eff = self.generate_downstream(n_dc, vals, [tx_updates[q] for q in sel], tokens)
+            for q, e in zip(sel, effs):
+                out[q] = e
+            ok = [i for i, e in enumerate(effs) if not (isinstance(e, tuple) and e and e[0] == "error")]
+            if not ok:
+                continue
+            ws = WriteSet([(eff.updates.entries[i][0], eff.updates.entries[i][1], [effs[i]]) for i in ok])
+            hb = self.materialize_eager_rows(n_dc, vals, ws, [set_capacity] * len(ok))
+            for k, i in enumerate(ok):
+                if int(hb.status[k]) != 0:
+                    raise abi.AmError(f"update_rounds: folding update {sel[i]} failed (status {int(hb.status[k])})")
+                r, t = eff.updates.entries[i][0], eff.updates.entries[i][1]
+                vals[r] = (t, hb.value(k))
+        return out
 
     def __del__(self):
         try:

@@ -376,3 +376,184 @@ class WriteSet:
         return (int(self.eff_meta[q]), int(self.p0[q]), int(self.p1[q]),
                 [int(w) for w in self.var_data[int(self.var_off[q]):int(self.var_off[q + 1])]])
 
+    @classmethod
+    def from_columns(cls, row, type_, eff_off, eff_meta, p0, p1, var_off, var_data, entries) -> "WriteSet":
+        """A write set over columns already in the ABI's encoding (Effects.as_writeset)."""
+        ws = cls.__new__(cls)
+        ws.entries = entries
+        ws.n_ws, ws.n_eff, ws.n_var = len(entries), int(eff_off[-1]), int(var_off[-1])
+        c = lambda a, dt: np.ascontiguousarray(a if len(a) else [0], dt)  # noqa: E731
+        ws.row, ws.type, ws.eff_off = c(row, U64), c(type_, np.uint8), np.ascontiguousarray(eff_off, U64)
+        ws.eff_meta, ws.p0, ws.p1 = c(eff_meta, np.uint8), c(p0, U64), c(p1, U64)
+        ws.var_off, ws.var_data = np.ascontiguousarray(var_off, U64), c(var_data, U64)
+        return ws
+
+
+def _u64(x: int) -> int:
+    return int(x) & 0xFFFFFFFFFFFFFFFF
+
+
+def _i64(x: int) -> int:
+    x = int(x) & 0xFFFFFFFFFFFFFFFF
+    return x - (1 << 64) if x >> 63 else x
+
+
+def decode_effect(type_: int, meta: int, p0: int, p1: int, words: Sequence[int]):
+    """The inverse of encode_effect: an effect's columns -> the shape encode_effect takes."""
+    kind = (meta >> 5) & 3
+    words = [int(w) for w in words]
+    if type_ == abi.AM_PN:
+        return _i64(p0)
+    if type_ == abi.AM_LWW:
+        return (int(p0), int(p1))
+    if type_ == abi.AM_MVREG:
+        return ("reset", words) if kind == 1 else ("assign", int(p0), int(p1), words)
+    if type_ == abi.AM_AWSET:
+        out, q = [], 0
+        while q < len(words):
+            e, na, nr = words[q:q + 3]
+            out.append((e, words[q + 3:q + 3 + na], words[q + 3 + na:q + 3 + na + nr]))
+            q += 3 + na + nr
+        return out
+    if type_ == abi.AM_BCOUNTER:
+        frm, to = int(p1) & 0xFF, (int(p1) >> 8) & 0xFF
+        if kind == 2:
+            return ("transfer", _i64(p0), to, frm)
+        return ("increment" if kind == 0 else "decrement", _i64(p0), frm)
+    raise ValueError(type_)
+
+
+class Updates:
+    """am_updates in host memory: client updates for some rows of a value batch, the input of
+    generate_downstream_op/6 (src/clocksi_downstream.erl:41-68).
+
+    entries: [(row, type, update)].  Updates per type (labels are u64, as the codec interns them):
+      PN        ("increment", N) | ("decrement", N)
+      LWW       ("assign", ts, value)               ts = the caller's make_micro_epoch()
+      AWSET     ("add", E) | ("add_all", [E]) | ("remove", E) | ("remove_all", [E]) | ("reset",)
+      MVREG     ("assign", Value) | ("reset",)
+      BCOUNTER  ("increment", (N, Dc)) | ("decrement", (N, Dc)) | ("transfer", (N, To, From))
+    The element lists are sorted and deduplicated here (lists:usort).  tokens: a callable returning
+    one fresh interned token per call -- one per added element (in element order) and one per MV
+    assign; self.tokens[i] lists the ones update i took.  An update given as ("raw", op, a0, a1,
+    [words]) is encoded as is (malformed inputs)."""
+
+    def __init__(self, entries: Sequence[Tuple[int, int, Sequence[Any]]], tokens=None):
+        self.entries = [(int(r), int(t), tuple(u)) for r, t, u in entries]
+        n = len(self.entries)
+        self.n_up = n
+        row, typ, op, a0, a1, var, var_off = [], [], [], [], [], [], [0]
+        self.tokens: List[List[int]] = []
+
+        def fresh():
+            if tokens is None:
+                raise ValueError("an add / assign update needs fresh tokens")
+            return int(tokens())
+        for r, t, u in self.entries:
+            o, x, y, words, took = self._encode(t, u, fresh)
+            row.append(r), typ.append(t), op.append(o), a0.append(_u64(x)), a1.append(_u64(y))
+            var += [_u64(w) for w in words]
+            var_off.append(len(var))
+            self.tokens.append(took)
+        self.n_var = len(var)
+        self.row = np.asarray(row or [0], U64)
+        self.type = np.asarray(typ or [0], np.uint8)
+        self.op = np.asarray(op or [0], np.uint8)
+        self.a0, self.a1 = np.asarray(a0 or [0], U64), np.asarray(a1 or [0], U64)
+        self.var_off = np.asarray(var_off, U64)
+        self.var_data = np.asarray(var or [0], U64)
+
+    @staticmethod
+    def _encode(t: int, u, fresh):
+        name = u[0]
+        if name == "raw":
+            return int(u[1]), u[2], u[3], list(u[4]), []
+        if t == abi.AM_PN:
+            return {"increment": abi.AM_UP_PN_INCREMENT, "decrement": abi.AM_UP_PN_DECREMENT}[name], u[1], 0, [], []
+        if t == abi.AM_LWW:
+            if name != "assign":
+                raise ValueError(u)
+            return abi.AM_UP_LWW_ASSIGN, u[1], u[2], [], []
+        if t == abi.AM_AWSET:
+            if name == "reset":
+                return abi.AM_UP_AW_RESET, 0, 0, [], []
+            elems = [u[1]] if name in ("add", "remove") else list(u[1])
+            elems = sorted({_u64(e) for e in elems})
+            if name in ("add", "add_all"):
+                took = [fresh() for _ in elems]
+                return abi.AM_UP_AW_ADD, 0, 0, [w for e, k in zip(elems, took) for w in (e, k)], took
+            if name in ("remove", "remove_all"):
+                return abi.AM_UP_AW_REMOVE, 0, 0, elems, []
+            raise ValueError(u)
+        if t == abi.AM_MVREG:
+            if name == "reset":
+                return abi.AM_UP_MV_RESET, 0, 0, [], []
+            if name != "assign":
+                raise ValueError(u)
+            tok = fresh()
+            return abi.AM_UP_MV_ASSIGN, u[1], tok, [], [tok]
+        if t == abi.AM_BCOUNTER:
+            if name == "transfer":
+                amount, to, frm = u[1]
+                return abi.AM_UP_BC_TRANSFER, amount, int(frm) | (int(to) << 8), [], []
+            amount, dc = u[1]
+            return {"increment": abi.AM_UP_BC_INCREMENT, "decrement": abi.AM_UP_BC_DECREMENT}[name], amount, dc, [], []
+        raise ValueError(t)
+
+    def as_struct(self) -> abi.am_updates:
+        s = abi.am_updates()
+        s.n_up, s.n_var = self.n_up, self.n_var
+        p = lambda a: a.ctypes.data  # noqa: E731
+        s.row, s.type, s.op, s.a0, s.a1 = p(self.row), p(self.type), p(self.op), p(self.a0), p(self.a1)
+        s.var_off, s.var_data = p(self.var_off), p(self.var_data)
+        self._struct = s
+        return s
+
+
+class Effects:
+    """am_effects in host memory for n_up updates, and its decoding: effect i in the shape
+    encode_effect takes, or ('error', status)."""
+
+    def __init__(self, updates: Updates, var_cap: int):
+        n = updates.n_up
+        self.updates, self.n_up, self.var_cap = updates, n, int(var_cap)
+        self.eff_off = np.zeros(n + 1, U64)
+        self.eff_meta = np.zeros(max(n, 1), np.uint8)
+        self.p0, self.p1 = np.zeros(max(n, 1), U64), np.zeros(max(n, 1), U64)
+        self.var_off = np.zeros(n + 1, U64)
+        self.var_data = np.zeros(max(self.var_cap, 1), U64)
+        self.n_var = np.zeros(1, U64)
+        self.avail = np.zeros(max(n, 1), np.int64)
+        self.status = np.full(max(n, 1), 99, np.int32)
+
+    def as_struct(self) -> abi.am_effects:
+        s = abi.am_effects()
+        s.var_cap = self.var_cap
+        p = lambda a: a.ctypes.data  # noqa: E731
+        s.eff_off, s.eff_meta, s.p0, s.p1 = p(self.eff_off), p(self.eff_meta), p(self.p0), p(self.p1)
+        s.var_off, s.var_data, s.n_var, s.avail = p(self.var_off), p(self.var_data), p(self.n_var), p(self.avail)
+        self._struct = s
+        return s
+
+    def words(self, i: int) -> List[int]:
+        return [int(w) for w in self.var_data[int(self.var_off[i]):int(self.var_off[i + 1])]]
+
+    def effect(self, i: int):
+        st = int(self.status[i])
+        if st != 0:
+            return ("error", st)
+        return decode_effect(self.updates.entries[i][1], int(self.eff_meta[i]), int(self.p0[i]), int(self.p1[i]),
+                             self.words(i))
+
+    def effects(self) -> list:
+        return [self.effect(i) for i in range(self.n_up)]
+
+    def as_writeset(self) -> WriteSet:
+        """The updates' rows and types with these columns as the write set they are (n_ws = n_eff
+        = n_up); a failed update's effect carries AM_META_BAD."""
+        n = self.n_up
+        ents = [(r, t, ["bad" if self.status[i] != 0 else self.effect(i)])
+                for i, (r, t, _) in enumerate(self.updates.entries)]
+        nv = int(self.var_off[n])
+        return WriteSet.from_columns(self.updates.row[:n], self.updates.type[:n], self.eff_off, self.eff_meta[:n],
+                                     self.p0[:n], self.p1[:n], self.var_off, self.var_data[:nv], ents)

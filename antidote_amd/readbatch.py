@@ -23,7 +23,7 @@ import numpy as np
 
 from . import abi
 from .materializer import Materializer, Vnode
-from .oplog import HostBatch, Op, Read, WriteSet
+from .oplog import Effects, HostBatch, Op, Read, Updates, WriteSet
 
 
 class PendingRead:
@@ -124,6 +124,47 @@ class PartitionedReader:
         """Per object ('ok', Value, NewLastOp, LastOpCt, IsNewSS, Count, flags) or
         ('error', status) -- AM_ERR_COLD_PATH when the read needs the log -- in request order."""
         return self.submit(objects, snapshot_time, txid, write_set=write_set).result()
+
+    def update_objects(self, objects_updates: Sequence[tuple], snapshot_time: Dict[int, int],
+                       txid: Optional[int] = None, write_set: Optional[Dict[int, Sequence]] = None, tokens=None,
+                       set_capacity: int = 4096, var_cap: Optional[int] = None):
+        """An update transaction's step for [(Key, Type, update or None)], keys distinct: the
+        read_objects of every request with write_set (the transaction's effects so far) folded in,
+        then Type:downstream/2 of the given updates on those values -- all on the device
+        (am_update_objects_submit); only the effects come back.  Returns ([effect |
+        ('error', status) | None per request], [avail or None per request], Effects)."""
+        n = len(objects_updates)
+        parts = np.zeros(max(n, 1), np.uint32)
+        reads = []
+        for i, (key, type_, _) in enumerate(objects_updates):
+            if key not in self.where:
+                raise KeyError(f"key {key} has no ops cache entry on this node")
+            parts[i], local = self.where[key]
+            reads.append(Read(local, type_, dict(snapshot_time), txid))
+        hb = HostBatch(self.n_dc, reads, [set_capacity] * n)
+        b, _ = hb.structs()
+        named = [i for i, (_, _, u) in enumerate(objects_updates) if u is not None]
+        ups = Updates([(i, objects_updates[i][1], objects_updates[i][2]) for i in named], tokens)
+        eff = Effects(ups, 4 * (set_capacity * len(named) + ups.n_var) if var_cap is None else var_cap)
+        ws = w = None
+        if write_set:
+            ws = WriteSet([(i, t, write_set[k]) for i, (k, t, _) in enumerate(objects_updates) if write_set.get(k)])
+            w = ws.as_struct()
+        u, e = ups.as_struct(), eff.as_struct()
+        t = ctypes.c_void_p()
+        abi.check(self.mat.L.am_update_objects_submit(self.vnode.handle, self.n_partitions,
+                                                      self.part_key_base.ctypes.data, parts.ctypes.data, ctypes.byref(b),
+                                                      hb.o_set_off.ctypes.data, ctypes.byref(w) if w is not None else None,
+                                                      ctypes.byref(u), ctypes.byref(e), eff.status.ctypes.data,
+                                                      ctypes.byref(t)), "am_update_objects_submit")
+        pr = PendingRead(t, hb, (b, parts, ws, w, ups, u, eff, e), owner=self)
+        self._pending.add(pr)
+        abi.check(pr.wait(), "am_update_objects")
+        effects: List = [None] * n
+        avail: List = [None] * n
+        for q, i in enumerate(named):
+            effects[i], avail[i] = eff.effect(q), int(eff.avail[q])
+        return effects, avail, eff
 
     def close(self):
         for pr in list(self._pending):

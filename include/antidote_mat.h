@@ -47,6 +47,8 @@
  *                           generate_downstream_op/6 (src/clocksi_downstream.erl:41-68) call it
  *   am_read_objects_ws_*    the read_objects fan-out with apply_tx_updates_to_snapshot/4
  *                           (src/clocksi_interactive_coord.erl:486-507, 883-894) on the device
+ *   am_generate_downstream  clocksi_downstream:generate_downstream_op/6 (src/clocksi_downstream.erl:
+ *   am_update_objects_*     41-68), batched: Type:downstream/2 on the state read, on the device
  *   am_key_partition        log_utilities:get_key_partition/1 + convert_key/1: integer
  *   am_key_partition_bytes  keys, binaries (list_to_integer text or SHA-1 chash_key) and
  *                           other terms (src/log_utilities.erl:60-79,100-118)
@@ -100,6 +102,7 @@ enum am_status {
   AM_ERR_CAPACITY = 4,              /* set result larger than the caller's capacity */
   AM_ERR_COLD_PATH = 5,             /* no cached snapshot at or below the read clock:
                                        get_from_snapshot_log (the log, not the cache) */
+  AM_ERR_NO_PERMISSIONS = 6,        /* {error, no_permissions} (am_generate_downstream)     */
   AM_ERR_INVALID = -1,
   AM_ERR_HIP = -2,
   AM_ERR_RCCL = -3,
@@ -639,6 +642,110 @@ int am_read_objects_ws_host(am_vnode *v, uint32_t n_parts, const uint64_t *part_
 int am_read_objects_ws_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
                               const am_read_batch *host_batch, const am_writeset *host_ws, am_read_result *host_res,
                               am_ticket **out);
+
+/* ---- downstream generation on the device (am_downstream.hip) ----
+ * clocksi_downstream:generate_downstream_op/6 (src/clocksi_downstream.erl:41-68) for a batch: a
+ * client update plus the state it read (the snapshot with the transaction's own writes folded in,
+ * am_materialize_eager / am_read_objects_ws_*) becomes the effect Type:downstream/2 returns, in
+ * am_writeset's / am_op_log's payload encoding.  The states never leave the device.
+ *
+ * Update op codes per type and their arguments:
+ *   PN        AM_UP_PN_INCREMENT / _DECREMENT    a0 = N (int64)
+ *   LWW       AM_UP_LWW_ASSIGN                   a0 = timestamp (the caller's make_micro_epoch()),
+ *                                                a1 = value
+ *   AWSET     AM_UP_AW_ADD      var = [elem, token] pairs, elems strictly ascending (add, add_all
+ *                               after lists:usort; one fresh token per element)
+ *             AM_UP_AW_REMOVE   var = elems, strictly ascending (remove, remove_all)
+ *             AM_UP_AW_RESET    no arguments
+ *   MVREG     AM_UP_MV_ASSIGN   a0 = value, a1 = the fresh token;  AM_UP_MV_RESET  no arguments
+ *   BCOUNTER  AM_UP_BC_INCREMENT / _DECREMENT    a0 = N (int64), a1 = DC index
+ *             AM_UP_BC_TRANSFER                  a0 = N, a1 = from | (to << 8)
+ * Tokens come from the caller, fresh and interned through the codec before the call. */
+#define AM_UP_PN_INCREMENT 0
+#define AM_UP_PN_DECREMENT 1
+#define AM_UP_LWW_ASSIGN 0
+#define AM_UP_AW_ADD 0
+#define AM_UP_AW_REMOVE 1
+#define AM_UP_AW_RESET 2
+#define AM_UP_MV_ASSIGN 0
+#define AM_UP_MV_RESET 1
+#define AM_UP_BC_INCREMENT 0
+#define AM_UP_BC_DECREMENT 1
+#define AM_UP_BC_TRANSFER 2
+typedef struct am_updates {          /* one client update per entry */
+  uint64_t n_up, n_var;
+  const uint64_t *row;               /* [n_up] row of the input values / in_status, distinct */
+  const uint8_t  *type;              /* [n_up] am_type */
+  const uint8_t  *op;                /* [n_up] AM_UP_* */
+  const uint64_t *a0, *a1;           /* [n_up] scalar arguments (table above) */
+  const uint64_t *var_off;           /* [n_up+1] or NULL (no update has variable arguments) */
+  const uint64_t *var_data;          /* [n_var] set elements / [elem, token] pairs */
+} am_updates;
+/* out: one effect per update.  row and type of the updates together with these columns are a
+ * valid am_writeset with n_ws = n_eff = n_up (eff_off = 0..n_up) and n_var = var_cap (a bound of
+ * *n_var, which can stay on the device): device pointers go straight into am_materialize_eager,
+ * or into a dev_new log's payload columns. */
+typedef struct am_effects {
+  uint64_t var_cap;
+  uint64_t *eff_off;                 /* [n_up+1] = 0..n_up */
+  uint8_t  *eff_meta; uint64_t *p0, *p1;   /* [n_up] */
+  uint64_t *var_off;                 /* [n_up+1] */
+  uint64_t *var_data;                /* [var_cap] */
+  uint64_t *n_var;                   /* [1] words needed */
+  int64_t  *avail;                   /* [n_up] or NULL */
+} am_effects;
+/* A 256-thread workgroup instead of a wavefront writes an effect that copies more than this many
+ * state pairs whole (an add-wins-set reset, an MV assign / reset): one full workgroup pass. */
+#define AM_DS_TILE_WG 256u
+/* Effect i / out_status[i] = Type:downstream(update i, the value at row[i] of dev_in).  Three
+ * steps on the context stream with no host readback: sizes and statuses, an exclusive scan into
+ * var_off (total in *n_var), the fill.  dev_in is not written.  Effects (the reference's rules;
+ * antidote_crdt's downstream/2 is not vendored, DESIGN.md 4c''):
+ *   PN        p0 = N / -N, no state read         LWW  p0 = timestamp, p1 = value, no state read
+ *   AWSET     add / remove: per requested element {E, [Token] or [], the current tokens of E};
+ *             reset: {E, [], Tokens} for every element of the state, in state order
+ *   MVREG     AM_MV_ASSIGN p0 = value, p1 = token / AM_MV_RESET; var = every token of the state
+ *   BCOUNTER  AM_BC_INCREMENT p0 = N, p1 = dc | dc << 8; an increment of N < 0 is a decrement of
+ *             -N (src/bcounter_mgr.erl:89-90); AM_BC_DECREMENT / AM_BC_TRANSFER when
+ *             localPermissions(dc / from) >= N, else AM_ERR_NO_PERMISSIONS (:120-129).
+ *             avail[i] (if given) = the local permissions for decrements and transfers
+ *             (bcounter_mgr queues Amount - Available on a refusal), 0 for every other update
+ * Statuses:
+ *   in_status[row[i]] != AM_OK    copied to out_status[i] for set / MV / bounded-counter updates
+ *                                 ({error, {gen_downstream_read_failed, Reason}},
+ *                                 src/clocksi_downstream.erl:51-52); PN and LWW ignore it
+ *   AM_ERR_INVALID                an unknown type or op (wins over the pass-through); set
+ *                                 elements not strictly ascending or argument offsets outside
+ *                                 var_data; a bounded-counter amount <= 0 after the sign rule; a DC
+ *                                 index >= n_dc; a set / MV / bounded-counter update whose input
+ *                                 lacks set columns; and for EVERY update of the call when two
+ *                                 updates name one row (two updates of one key are two calls with
+ *                                 an eager fold between them, src/clocksi_interactive_coord.erl:986)
+ *   AM_ERR_OVERFLOW               negating INT64_MIN; local permissions outside int64 (summed
+ *                                 exactly in 128 bits)
+ *   AM_ERR_NO_PERMISSIONS         {error, no_permissions}
+ *   AM_ERR_CAPACITY               *n_var > var_cap: every update that needs variable words gets it
+ *                                 and no variable word is written; *n_var holds the needed total
+ * An update with a non-OK status has no variable words (var_off[i+1] == var_off[i]) and
+ * AM_META_BAD in eff_meta[i], so its effect can never be applied half-written. */
+int am_generate_downstream(am_ctx *ctx, uint32_t n_dc, const am_updates *dev_up, const am_values *dev_in,
+                           const int32_t *in_status /* or NULL */, am_effects *dev_eff, int32_t *out_status);
+/* The same with host pointers; blocks.  Only the rows the updates name are read.  A repeated row
+ * makes the call itself return AM_ERR_INVALID. */
+int am_generate_downstream_host(am_ctx *ctx, uint32_t n_dc, const am_updates *host_up, const am_values *host_in,
+                                const int32_t *in_status /* or NULL */, am_effects *host_eff, int32_t *out_status);
+/* The coordinator-level call: am_read_objects_ws_host / _submit of the batch (request i is row i;
+ * host_ws or NULL: the transaction's write set so far), the values left in the device result with
+ * set_off [n_reads + 1] as their capacities, then am_generate_downstream of host_up on them.  Only
+ * the effects, out_status [n_up] and avail come back (one readback of *n_var sizes the copy).  The
+ * requests must name distinct keys (AM_ERR_INVALID otherwise).  Every buffer must stay valid
+ * until the call (the ticket's wait) returns. */
+int am_update_objects_host(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
+                           const am_read_batch *host_batch, const uint64_t *set_off, const am_writeset *host_ws,
+                           const am_updates *host_up, am_effects *host_eff, int32_t *out_status);
+int am_update_objects_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
+                             const am_read_batch *host_batch, const uint64_t *set_off, const am_writeset *host_ws,
+                             const am_updates *host_up, am_effects *host_eff, int32_t *out_status, am_ticket **out);
 
 /* ---- op-cache ingestion + garbage collection ----
  * Builds a new store from `st` (st is unchanged; destroy it when no read uses it):
