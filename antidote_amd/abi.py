@@ -114,6 +114,25 @@ class am_effects(ctypes.Structure):
     ]
 
 
+class am_commits(ctypes.Structure):
+    _fields_ = [
+        ("n_tx", c_uint64), ("n_eff", c_uint64), ("n_var", c_uint64),
+        ("dc", c_void_p), ("commit_time", c_void_p), ("snap_vc", c_void_p), ("snap_pres", c_void_p),
+        ("txid", c_void_p), ("eff_off", c_void_p), ("key", c_void_p), ("type", c_void_p),
+        ("eff_meta", c_void_p), ("p0", c_void_p), ("p1", c_void_p), ("var_off", c_void_p), ("var_data", c_void_p),
+    ]
+
+
+class am_commit_log(ctypes.Structure):
+    _fields_ = [
+        ("cap_ops", c_uint64), ("cap_var", c_uint64), ("snap_stride", c_uint64),
+        ("keys", c_void_p), ("key_off", c_void_p), ("key_type", c_void_p), ("key_flags", c_void_p),
+        ("op_meta", c_void_p), ("commit_time", c_void_p), ("snap_vc", c_void_p), ("snap_pres", c_void_p),
+        ("op_txid", c_void_p), ("p0", c_void_p), ("p1", c_void_p), ("var_off", c_void_p), ("var_data", c_void_p),
+        ("src", c_void_p),
+    ]
+
+
 class am_synth_params(ctypes.Structure):
     _fields_ = [
         ("seed", c_uint64), ("n_keys", c_uint64), ("ops_per_key", c_uint32), ("n_dc", c_uint32),
@@ -152,6 +171,8 @@ AM_UP_AW_ADD, AM_UP_AW_REMOVE, AM_UP_AW_RESET = 0, 1, 2
 AM_UP_MV_ASSIGN, AM_UP_MV_RESET = 0, 1
 AM_UP_BC_INCREMENT, AM_UP_BC_DECREMENT, AM_UP_BC_TRANSFER = 0, 1, 2
 AM_DS_TILE_WG = 256
+# am_commit_build: why a batch is invalid (AM_COMMIT_BAD_*)
+AM_COMMIT_BAD_DC, AM_COMMIT_BAD_EFF_OFF, AM_COMMIT_BAD_VAR_OFF, AM_COMMIT_BAD_TYPE, AM_COMMIT_BAD_KEY = 1, 2, 4, 8, 16
 
 
 # (name, restype, argtypes) of every exported symbol declared in include/antidote_mat.h
@@ -236,6 +257,9 @@ SIGNATURES = [
     ("am_update_objects_submit", c_int, [c_void_p, c_uint32, c_void_p, c_void_p, POINTER(am_read_batch), c_void_p,
                                          POINTER(am_writeset), POINTER(am_updates), POINTER(am_effects), c_void_p,
                                          POINTER(c_void_p)]),
+    ("am_commit_build", c_int, [c_void_p, c_uint32, POINTER(am_commits), c_uint32, POINTER(am_commit_log),
+                                POINTER(am_op_log), POINTER(c_uint64), POINTER(c_uint32)]),
+    ("am_vnode_commit_host", c_int, [c_void_p, POINTER(am_commits)]),
     ("am_codec_create", c_int, [POINTER(c_void_p)]),
     ("am_codec_destroy", c_int, [c_void_p]),
     ("am_codec_intern", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),

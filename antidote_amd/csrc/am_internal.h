@@ -13,7 +13,7 @@
 
 #include "../../include/antidote_mat.h"
 
-enum { AM_SCR_PLAN = 0, AM_SCR_BIGMETA = 1, AM_SCR_BIGREC = 2, AM_SCR_ROWS = 3, AM_SCR_GRP = 4, AM_SCR_SPARE = 5, AM_SCR_SNAP = 6, AM_SCR_GC = 7, AM_SCR_SIZES = 8, AM_SCR_MISC = 9, AM_SCR_INCL = 10, AM_SCR_ROUTE = 11, AM_SCR_EAGER = 12, AM_SCR_DOWN = 13, AM_N_SCR = 14 };
+enum { AM_SCR_PLAN = 0, AM_SCR_BIGMETA = 1, AM_SCR_BIGREC = 2, AM_SCR_ROWS = 3, AM_SCR_GRP = 4, AM_SCR_SPARE = 5, AM_SCR_SNAP = 6, AM_SCR_GC = 7, AM_SCR_SIZES = 8, AM_SCR_MISC = 9, AM_SCR_INCL = 10, AM_SCR_ROUTE = 11, AM_SCR_EAGER = 12, AM_SCR_DOWN = 13, AM_SCR_COMMIT = 14, AM_N_SCR = 15 };
 
 struct am_ctx {
   int device = 0;
@@ -237,6 +237,20 @@ int am_eager_apply_result(am_ctx *ctx, uint32_t n_dc, const am_writeset *host_ws
 // stream; only the effects, statuses and avail are copied to the host.  am_update_objects_*.
 int am_downstream_apply_result(am_ctx *ctx, uint32_t n_dc, uint64_t n_rows, const am_updates *host_up,
                                const am_read_result *dr, am_effects *host_eff, int32_t *out_status);
+
+// The commit log builder's helpers for the vnode (am_commit.hip); every pointer a device pointer.
+// am_commit_slice: the ops [beg_i, end_i) of key idx_i of a built log B, for m entries, as a smaller
+// CSR log in out's buffers: ooff [m+1] = the slice's key_off, voff [m+1] = its keys' first variable
+// words (both planned on the host), n_out / v_out their last entries.  For rounds that stop at a GC
+// trigger.
+int am_commit_slice(am_ctx *c, const am_op_log &B, uint64_t m, const uint64_t *idx, const uint64_t *beg,
+                    const uint64_t *ooff, const uint64_t *voff, uint64_t n_out, uint64_t v_out, const am_commit_log &out,
+                    am_op_log *out_log);
+// am_commit_spread: key_off [n_keys+1] / key_type / key_flags [n_keys] over all keys of a vnode from a
+// log T over the m ascending keys `keys` (untouched keys empty, AM_PN): with them T's op columns
+// are a log over the whole key space, for the rebuild fallback.
+int am_commit_spread(am_ctx *c, const am_op_log &T, const uint64_t *keys, uint64_t n_keys, uint64_t *off, uint8_t *type,
+                     uint8_t *flags);
 
 // host arrays -> one device arena (stream-ordered copies); the host sources outlive the call
 struct am_stage {

@@ -7,6 +7,10 @@
 //                         internal_read(Key, Type, Op.snapshot_time, ignore, [], true) and
 //                         then appends.  load_ops/2 (:312-319) replays the log through the
 //                         same call.
+//   am_vnode_commit_host  the same for a batch of committed transactions' effects as they are
+//                         (clocksi_vnode:commit/5 -> update_materializer/3, src/clocksi_vnode.erl:
+//                         499-531, 634-657): the op log over the touched keys is built on the
+//                         device (am_commit.hip), the rounds below plan over it
 //   am_vnode_read_host    internal_read/7 (:371-376) for a batch, ShouldGC per read; a key
 //                         read several times in one batch is served in batch order.
 // A GC (snapshot_insert_gc/4, :515-563: the dict reached SNAPSHOT_THRESHOLD entries, or
@@ -254,6 +258,21 @@ int read_round(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, a
   return gc.empty() ? AM_OK : prune(v, gc);
 }
 
+// Where insert_keys' new ops come from: a host log (am_vnode_insert_host) or the log
+// am_commit_build left on the device (am_vnode_commit_host).  Ops are named by their position in
+// the source's CSR, keys by their index in it.
+struct OpSource {
+  virtual ~OpSource() = default;
+  virtual uint8_t key_type(uint64_t srck) const = 0;
+  // op p's snapshot_time: its presence bits (every DC when the source has none) and entry d
+  virtual uint32_t snap_pres(uint64_t p) const = 0;
+  virtual uint64_t snap_vc(uint64_t p, uint64_t d) const = 0;
+  // the ops [beg_i, end_i) of source key srck_i onto vnode key keys_i: in place, or a whole-store
+  // rebuild with the new ops when a key outgrows its room
+  virtual int append(am_vnode *v, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
+                     const std::vector<uint64_t> &beg, const std::vector<uint64_t> &end) = 0;
+};
+
 // host op log holding the ops [beg_i, end_i) of source key src_i for every entry i of a list
 // (same columns as src); key i of the slice is the list's entry i
 struct HostSlice {
@@ -311,11 +330,21 @@ struct HostSlice {
   }
 };
 
-// appends src's ops [beg_i, end_i) of source key src_i to vnode key keys_i (ids OpCounter +
-// 1, ...): in place, or a whole-store rebuild with the new ops when a key outgrows its room
-int append(am_vnode *v, const am_op_log &src, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
-           const std::vector<uint64_t> &beg, const std::vector<uint64_t> &end) {
-  if (keys.empty()) return AM_OK;
+// a host log: every round's ops are copied into a slice and uploaded through a temporary store
+struct HostLogSource : OpSource {
+  const am_op_log &src;
+  explicit HostLogSource(const am_op_log &h) : src(h) {}
+  uint8_t key_type(uint64_t srck) const override { return src.key_type[srck]; }
+  uint32_t snap_pres(uint64_t p) const override { return src.snap_pres ? src.snap_pres[p] : 0xFFFFFFFFu; }
+  uint64_t snap_vc(uint64_t p, uint64_t d) const override {
+    return src.snap_vc[d * (src.snap_stride ? src.snap_stride : src.n_ops) + p];
+  }
+  int append(am_vnode *v, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
+             const std::vector<uint64_t> &beg, const std::vector<uint64_t> &end) override;
+};
+
+int HostLogSource::append(am_vnode *v, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
+                          const std::vector<uint64_t> &beg, const std::vector<uint64_t> &end) {
   HostSlice hs(src, srck, beg, end);
   am_store *tmp = nullptr;
   int rc = am_store_create(v->ctx, &hs.log, &tmp);
@@ -357,6 +386,14 @@ int append(am_vnode *v, const am_op_log &src, const std::vector<uint64_t> &keys,
     swap_store(v, ns);
     ++v->rebuilds;
   }
+  return AM_OK;
+}
+
+// appends src's ops [beg_i, end_i) of source key srck_i to vnode key keys_i (ids OpCounter + 1, ...)
+int append(am_vnode *v, OpSource &src, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
+           const std::vector<uint64_t> &beg, const std::vector<uint64_t> &end) {
+  if (keys.empty()) return AM_OK;
+  if (int rc = src.append(v, keys, srck, beg, end)) return rc;
   for (uint64_t i = 0; i < keys.size(); ++i) {
     v->len[keys[i]] += end[i] - beg[i];
     v->counter[keys[i]] += end[i] - beg[i];
@@ -386,8 +423,8 @@ struct HostResult {
 
 // op_insert_gc's GC reads: internal_read(Key, Type, Op.snapshot_time, ignore, [], true) for
 // vnode key keys_i at the trigger op trig_i of the source log
-int gc_reads(am_vnode *v, const am_op_log &src, std::vector<uint64_t> keys, std::vector<uint64_t> trig) {
-  const uint64_t nd = v->n_dc, ss = src.snap_stride ? src.snap_stride : src.n_ops;
+int gc_reads(am_vnode *v, const OpSource &src, std::vector<uint64_t> keys, std::vector<uint64_t> trig) {
+  const uint64_t nd = v->n_dc;
   const uint32_t all = nd >= 32 ? 0xFFFFFFFFu : ((1u << nd) - 1u);
   // the read's value is discarded; a read short of set capacity stored nothing and reruns
   for (uint64_t cap = 64; !keys.empty(); cap *= 4) {
@@ -398,8 +435,8 @@ int gc_reads(am_vnode *v, const am_op_log &src, std::vector<uint64_t> keys, std:
     for (uint64_t i = 0; i < n; ++i) {
       const uint64_t p = trig[i];
       type[i] = v->type[keys[i]];
-      rp[i] = src.snap_pres ? (src.snap_pres[p] & all) : all;
-      for (uint64_t d = 0; d < nd; ++d) vc[d * n + i] = ((rp[i] >> d) & 1u) ? src.snap_vc[d * ss + p] : 0;
+      rp[i] = src.snap_pres(p) & all;
+      for (uint64_t d = 0; d < nd; ++d) vc[d * n + i] = ((rp[i] >> d) & 1u) ? src.snap_vc(p, d) : 0;
     }
     am_read_batch b{};
     b.n_reads = n;
@@ -424,7 +461,7 @@ int gc_reads(am_vnode *v, const am_op_log &src, std::vector<uint64_t> keys, std:
 // distinct), each key oldest -> newest, in rounds: every key appends up to its next GC trigger
 // (one in-place apply for all of them), the triggered keys' GC reads run as one batch (and
 // prune in place), repeat.  Host work is O(touched keys) per round.
-int insert_keys(am_vnode *v, const am_op_log &h, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
+int insert_keys(am_vnode *v, OpSource &h, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
                 const std::vector<uint64_t> &beg, const std::vector<uint64_t> &end) {
   const uint64_t m = keys.size();
   std::vector<uint64_t> pos(beg);
@@ -437,7 +474,7 @@ int insert_keys(am_vnode *v, const am_op_log &h, const std::vector<uint64_t> &ke
     std::vector<uint64_t> ak, asrc, abeg, aend, tk, tp, next;
     for (uint64_t i : live) {
       const uint64_t k = keys[i];
-      if (!v->list_len[k]) v->list_len[k] = OPS_THRESHOLD, v->type[k] = h.key_type[srck[i]];  // ets:insert of a new tuple
+      if (!v->list_len[k]) v->list_len[k] = OPS_THRESHOLD, v->type[k] = h.key_type(srck[i]);  // ets:insert of a new tuple
       uint64_t p = pos[i], l = ref_len(v, k), c = v->counter[k];
       if (pending[i]) ++p, ++l, ++c;  // the trigger op goes in after its GC read
       uint64_t trig = ~0ull;
@@ -461,6 +498,89 @@ int insert_keys(am_vnode *v, const am_op_log &h, const std::vector<uint64_t> &ke
   }
   return AM_OK;
 }
+
+// the log am_commit_build left on the device (am_vnode_commit_host): a round that takes every built
+// key whole hands the built log to am_store_apply as it is, any other round its k_cm_slice; a key
+// that outgrows its room gets the round's log spread over the key space (k_cm_spread) for the one
+// rebuild.  No op is copied on the host, and nothing here walks the vnode's keys on the host but the
+// rebuild's capacity hint.
+struct DevLogSource : OpSource {
+  const am_commits &hc;           // the host batch
+  am_op_log built{};              // device
+  const uint64_t *d_keys = nullptr;  // device [n_touched]
+  std::vector<uint64_t> koff, bvoff;  // host copies of built.key_off [n_touched+1] and built.var_off [n_ops+1]
+  std::vector<uint8_t> ktype;     // built.key_type
+  std::vector<uint32_t> src;      // the batch effect of every built op
+  std::vector<uint32_t> tx_of;    // the transaction of every batch effect
+  uint64_t nd;
+  DevLogSource(const am_commits &h, uint64_t nd_) : hc(h), nd(nd_) {}
+  uint8_t key_type(uint64_t srck) const override { return ktype[srck]; }
+  uint32_t snap_pres(uint64_t p) const override { return hc.snap_pres ? hc.snap_pres[tx_of[src[p]]] : 0xFFFFFFFFu; }
+  uint64_t snap_vc(uint64_t p, uint64_t d) const override { return hc.snap_vc[(uint64_t)tx_of[src[p]] * nd + d]; }
+  int append(am_vnode *v, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
+             const std::vector<uint64_t> &beg, const std::vector<uint64_t> &end) override {
+    const uint64_t m = keys.size();
+    bool whole = m == built.n_keys;
+    for (uint64_t i = 0; whole && i < m; ++i) whole = srck[i] == i && beg[i] == koff[i] && end[i] == koff[i + 1];
+    am_op_log log = built;
+    const uint64_t *dk = d_keys;
+    am_stage st, sp;
+    auto done = [&](int rc) {
+      (void)hipStreamSynchronize(v->ctx->stream);
+      if (st.arena) am_dev_release(v->ctx, st.arena);
+      if (sp.arena) am_dev_release(v->ctx, sp.arena);
+      return rc;
+    };
+    if (!whole) {  // the round stops some key at a GC trigger: its part of the built log
+      std::vector<uint64_t> ooff(m + 1, 0), voff(m + 1, 0);
+      for (uint64_t i = 0; i < m; ++i) {
+        ooff[i + 1] = ooff[i] + (end[i] - beg[i]);
+        voff[i + 1] = voff[i] + (bvoff[end[i]] - bvoff[beg[i]]);
+      }
+      const uint64_t no = ooff[m], nv = voff[m];
+      const size_t i_k = st.add(keys.data(), m * 8), i_s = st.add(srck.data(), m * 8), i_b = st.add(beg.data(), m * 8);
+      const size_t i_oo = st.add(ooff.data(), (m + 1) * 8), i_vo = st.add(voff.data(), (m + 1) * 8);
+      const size_t o_ko = st.add(nullptr, (m + 1) * 8), o_kt = st.add(nullptr, m), o_kf = st.add(nullptr, m);
+      const size_t o_m = st.add(nullptr, no), o_ct = st.add(nullptr, no * 8), o_vc = st.add(nullptr, nd * no * 8);
+      const size_t o_sp = st.add(nullptr, no * 4), o_tx = st.add(nullptr, no * 8), o_p0 = st.add(nullptr, no * 8);
+      const size_t o_p1 = st.add(nullptr, no * 8), o_vf = st.add(nullptr, (no + 1) * 8), o_vd = st.add(nullptr, nv * 8 + 8);
+      if (int rc = st.upload(v->ctx)) return done(rc);
+      am_commit_log o{};
+      o.cap_ops = no, o.cap_var = nv, o.snap_stride = no;
+      o.key_off = st.dev<uint64_t>(o_ko), o.key_type = st.dev<uint8_t>(o_kt), o.key_flags = st.dev<uint8_t>(o_kf);
+      o.op_meta = st.dev<uint8_t>(o_m), o.commit_time = st.dev<uint64_t>(o_ct), o.snap_vc = st.dev<uint64_t>(o_vc);
+      o.snap_pres = st.dev<uint32_t>(o_sp), o.op_txid = st.dev<uint64_t>(o_tx), o.p0 = st.dev<uint64_t>(o_p0);
+      o.p1 = st.dev<uint64_t>(o_p1), o.var_off = st.dev<uint64_t>(o_vf), o.var_data = st.dev<uint64_t>(o_vd);
+      if (int rc = am_commit_slice(v->ctx, built, m, st.dev<uint64_t>(i_s), st.dev<uint64_t>(i_b), st.dev<uint64_t>(i_oo),
+                                   st.dev<uint64_t>(i_vo), no, nv, o, &log))
+        return done(rc);
+      dk = st.dev<uint64_t>(i_k);
+    }
+    int applied = 0;
+    int rc = am_store_apply_ex(v->ctx, v->st, m, dk, &log, nullptr, nullptr, nullptr, nullptr, nullptr, &applied);
+    if (rc) return done(rc);
+    if (applied) {
+      ++v->applies;
+      return done(AM_OK);
+    }
+    // the round's ops as CSR over every vnode key, one rebuild (every key's room regrown)
+    const size_t o_off = sp.add(nullptr, (v->n_keys + 1) * 8), o_t = sp.add(nullptr, v->n_keys), o_f = sp.add(nullptr, v->n_keys);
+    if ((rc = sp.upload(v->ctx))) return done(rc);
+    am_op_log all = log;
+    all.n_keys = v->n_keys;
+    all.key_off = sp.dev<uint64_t>(o_off), all.key_type = sp.dev<uint8_t>(o_t), all.key_flags = sp.dev<uint8_t>(o_f);
+    rc = am_commit_spread(v->ctx, log, dk, v->n_keys, sp.dev<uint64_t>(o_off), sp.dev<uint8_t>(o_t), sp.dev<uint8_t>(o_f));
+    if (rc) return done(rc);
+    am_store *ns = nullptr;
+    CapHint ch(v->ctx);
+    if ((rc = ch.upload(v, v->n_keys))) return done(rc);
+    rc = am_store_update_ex(v->ctx, v->st->dev, v->st->counter, &all, nullptr, nullptr, nullptr, nullptr, true, ch.p, &ns);
+    if (rc) return done(rc);
+    swap_store(v, ns);
+    ++v->rebuilds;
+    return done(AM_OK);
+  }
+};
 
 }  // namespace
 
@@ -523,7 +643,87 @@ int am_vnode_insert_host(am_vnode *v, const am_op_log *h) {
   std::vector<uint64_t> keys, beg, end;
   for (uint64_t k = 0; k < v->n_keys; ++k)
     if (h->key_off[k + 1] > h->key_off[k]) keys.push_back(k), beg.push_back(h->key_off[k]), end.push_back(h->key_off[k + 1]);
-  return insert_keys(v, *h, keys, keys, beg, end);
+  HostLogSource src(*h);
+  return insert_keys(v, src, keys, keys, beg, end);
+}
+
+int am_vnode_commit_host(am_vnode *v, const am_commits *h) {
+  if (!v || !h) return AM_ERR_INVALID;
+  AM_LOCK(v->ctx);
+  const uint64_t n = h->n_eff, nt = h->n_tx, nd = v->n_dc;
+  if (nt == 0 || n == 0) return n ? AM_ERR_INVALID : AM_OK;
+  if (!h->dc || !h->commit_time || !h->snap_vc || !h->eff_off || !h->key || !h->type || !h->eff_meta || !h->p0 || !h->p1 ||
+      (h->var_off && h->n_var && !h->var_data) || (n >> 32) || (nt >> 32)) {
+    am_set_error("am_vnode_commit_host: the batch lacks a column or holds 2^32 or more effects");
+    return AM_ERR_INVALID;
+  }
+  uint64_t maxk = 0;
+  for (uint64_t e = 0; e < n; ++e) maxk = h->key[e] > maxk ? h->key[e] : maxk;
+  if (maxk == ~0ull) {
+    am_set_error("am_vnode_commit_host: key 2^64 - 1 is outside every key space");
+    return AM_ERR_INVALID;
+  }
+  uint32_t key_bits = 1;
+  while (key_bits < 64 && (maxk >> key_bits)) ++key_bits;
+  AM_HIP(hipSetDevice(v->ctx->device));
+  // the batch and the built log in one arena: O(batch) up, keys / counts / src back
+  const bool var = h->var_off != nullptr;
+  const uint64_t nv = var ? h->n_var : 0;
+  am_stage st;
+  const size_t i_dc = st.add(h->dc, nt), i_ct = st.add(h->commit_time, nt * 8), i_vc = st.add(h->snap_vc, nt * nd * 8);
+  const size_t i_sp = st.add(h->snap_pres, h->snap_pres ? nt * 4 : 0), i_tx = st.add(h->txid, h->txid ? nt * 8 : 0);
+  const size_t i_eo = st.add(h->eff_off, (nt + 1) * 8), i_k = st.add(h->key, n * 8), i_t = st.add(h->type, n);
+  const size_t i_m = st.add(h->eff_meta, n), i_p0 = st.add(h->p0, n * 8), i_p1 = st.add(h->p1, n * 8);
+  const size_t i_vo = st.add(h->var_off, var ? (n + 1) * 8 : 0), i_vd = st.add(h->var_data, nv * 8);
+  const size_t o_k = st.add(nullptr, n * 8), o_ko = st.add(nullptr, (n + 1) * 8), o_kt = st.add(nullptr, n);
+  const size_t o_kf = st.add(nullptr, n), o_m = st.add(nullptr, n), o_ct = st.add(nullptr, n * 8);
+  const size_t o_vc = st.add(nullptr, nd * n * 8), o_sp = st.add(nullptr, n * 4), o_tx = st.add(nullptr, n * 8);
+  const size_t o_p0 = st.add(nullptr, n * 8), o_p1 = st.add(nullptr, n * 8), o_vo = st.add(nullptr, (n + 1) * 8);
+  const size_t o_vd = st.add(nullptr, nv * 8 + 8), o_src = st.add(nullptr, n * 4);
+  auto done = [&](int rc) {
+    (void)hipStreamSynchronize(v->ctx->stream);
+    if (st.arena) am_dev_release(v->ctx, st.arena);
+    return rc;
+  };
+  if (int rc = st.upload(v->ctx)) return done(rc);
+  am_commits dc = *h;
+  dc.n_var = nv;
+  dc.dc = st.dev<uint8_t>(i_dc), dc.commit_time = st.dev<uint64_t>(i_ct), dc.snap_vc = st.dev<uint64_t>(i_vc);
+  dc.snap_pres = h->snap_pres ? st.dev<uint32_t>(i_sp) : nullptr, dc.txid = h->txid ? st.dev<uint64_t>(i_tx) : nullptr;
+  dc.eff_off = st.dev<uint64_t>(i_eo), dc.key = st.dev<uint64_t>(i_k), dc.type = st.dev<uint8_t>(i_t);
+  dc.eff_meta = st.dev<uint8_t>(i_m), dc.p0 = st.dev<uint64_t>(i_p0), dc.p1 = st.dev<uint64_t>(i_p1);
+  dc.var_off = var ? st.dev<uint64_t>(i_vo) : nullptr, dc.var_data = var ? st.dev<uint64_t>(i_vd) : nullptr;
+  am_commit_log o{};
+  o.cap_ops = n, o.cap_var = nv, o.snap_stride = n;
+  o.keys = st.dev<uint64_t>(o_k), o.key_off = st.dev<uint64_t>(o_ko), o.key_type = st.dev<uint8_t>(o_kt);
+  o.key_flags = st.dev<uint8_t>(o_kf), o.op_meta = st.dev<uint8_t>(o_m), o.commit_time = st.dev<uint64_t>(o_ct);
+  o.snap_vc = st.dev<uint64_t>(o_vc), o.snap_pres = st.dev<uint32_t>(o_sp), o.op_txid = st.dev<uint64_t>(o_tx);
+  o.p0 = st.dev<uint64_t>(o_p0), o.p1 = st.dev<uint64_t>(o_p1), o.var_off = st.dev<uint64_t>(o_vo);
+  o.var_data = st.dev<uint64_t>(o_vd), o.src = st.dev<uint32_t>(o_src);
+  DevLogSource src(*h, nd);
+  uint64_t m = 0;
+  if (int rc = am_commit_build(v->ctx, v->n_dc, &dc, key_bits, &o, &src.built, &m, nullptr)) return done(rc);
+  src.d_keys = o.keys;
+  std::vector<uint64_t> keys(m);
+  src.koff.resize(m + 1), src.ktype.resize(m), src.src.resize(n), src.bvoff.resize(n + 1);
+  hipError_t e = hipMemcpyAsync(keys.data(), o.keys, m * 8, hipMemcpyDeviceToHost, v->ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(src.koff.data(), o.key_off, (m + 1) * 8, hipMemcpyDeviceToHost, v->ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(src.ktype.data(), o.key_type, m, hipMemcpyDeviceToHost, v->ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(src.src.data(), o.src, n * 4, hipMemcpyDeviceToHost, v->ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(src.bvoff.data(), o.var_off, (n + 1) * 8, hipMemcpyDeviceToHost, v->ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(v->ctx->stream);
+  if (e != hipSuccess) {
+    am_set_error("am_vnode_commit_host: %s", hipGetErrorString(e));
+    return done(AM_ERR_HIP);
+  }
+  src.tx_of.resize(n);
+  for (uint64_t t = 0; t < nt; ++t)  // the device found eff_off non-decreasing from 0 to n_eff
+    for (uint64_t q = h->eff_off[t]; q < h->eff_off[t + 1]; ++q) src.tx_of[q] = (uint32_t)t;
+  if (maxk >= v->n_keys)  // keys seen for the first time beyond the key space
+    if (int rc = grow_keys(v, maxk + 1)) return done(rc);
+  std::vector<uint64_t> srck(m), beg(src.koff.begin(), src.koff.end() - 1), end(src.koff.begin() + 1, src.koff.end());
+  for (uint64_t i = 0; i < m; ++i) srck[i] = i;
+  return done(insert_keys(v, src, keys, srck, beg, end));
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@ import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from . import abi
-from .oplog import Effects, HostBatch, HostLog, Op, Read, Updates, WriteSet
+from .oplog import Commits, Effects, HostBatch, HostLog, Op, Read, Updates, WriteSet
 
 IGNORE = None
 
@@ -367,6 +367,17 @@ class Vnode:
         s = log.as_struct()
         abi.check(self.mat.L.am_vnode_insert_host(self.handle, ctypes.byref(s)), "am_vnode_insert_host")
         self.n_keys = max(self.n_keys, len(ops_by_key))  # keys past the key space grow it
+
+    def commit(self, transactions):
+        """clocksi_vnode:commit/5 -> update_materializer/3 for a batch of committed transactions
+        (am_vnode_commit_host): op_insert_gc/3 for every effect, the op log built on the device.
+        transactions: a Commits, or what Commits takes -- [(dc, commit_time, snap, txid, [(key,
+        type, effect), ...])].  Host work is O(batch), whatever the vnode's key count."""
+        cm = transactions if isinstance(transactions, Commits) else Commits(self.n_dc, transactions)
+        s = cm.as_struct()
+        abi.check(self.mat.L.am_vnode_commit_host(self.handle, ctypes.byref(s)), "am_vnode_commit_host")
+        if cm.n_eff:
+            self.n_keys = max(self.n_keys, int(cm.key[:cm.n_eff].max()) + 1)  # keys past the key space grow it
 
     def read(self, reads: Sequence[Read], should_gc: Optional[Sequence[bool]] = None, set_capacity=None) -> HostBatch:
         """internal_read/7 per read (read.base_* ignored); ('error', AM_ERR_COLD_PATH) for the log path."""

@@ -557,3 +557,147 @@ class Effects:
         nv = int(self.var_off[n])
         return WriteSet.from_columns(self.updates.row[:n], self.updates.type[:n], self.eff_off, self.eff_meta[:n],
                                      self.p0[:n], self.p1[:n], self.var_off, self.var_data[:nv], ents)
+
+
+class Commits:
+    """am_commits in host memory: a batch of committed transactions, in the order the vnode commits
+    them, as clocksi_vnode:commit/5 -> update_materializer/3 (src/clocksi_vnode.erl:499-531,
+    634-657) and inter_dc_dep_vnode (src/inter_dc_dep_vnode.erl:150-152) hand them to the
+    materializer.
+
+    transactions: [(dc, commit_time, snap, txid, [(key, type, effect), ...])] -- the commit DC index
+    (the own DC, or a remote transaction's origin), TxCommitTime, vec_snapshot_time as {dc: time},
+    the am_txid id or None, and the effects oldest first, shaped as encode_effect takes them (the
+    string "bad": one Type:update/2 raises on).  snap_pres is kept only when some snapshot lacks a
+    DC, txid only when some transaction has one (0 for the others) -- among the transactions that
+    have effects, so the columns are those of a HostLog of the same ops."""
+
+    def __init__(self, n_dc: int, transactions: Sequence[Tuple[int, int, Dict[int, int], Optional[int], Sequence[Any]]]):
+        txs = [(int(d), int(ct), dict(sn), tx, list(effs)) for d, ct, sn, tx, effs in transactions]
+        key, typ, meta, p0, p1, var, var_off = [], [], [], [], [], [], [0]
+        for _, _, _, _, effs in txs:
+            for k, t, eff in effs:
+                bad = isinstance(eff, str) and eff == "bad"
+                kind, a, b, words = (0, 0, 0, []) if bad else encode_effect(t, eff)
+                key.append(int(k)), typ.append(int(t)), meta.append(abi.make_meta(0, kind, bad))
+                p0.append(_u64(a)), p1.append(_u64(b))
+                var += [_u64(w) for w in words]
+                var_off.append(len(var))
+        self._init_columns(n_dc, [(d, ct, sn, tx, len(effs)) for d, ct, sn, tx, effs in txs], key, typ, meta, p0, p1,
+                           var_off, var)
+
+    @classmethod
+    def from_columns(cls, n_dc: int, transactions, key, type_, eff_meta, p0, p1, var_off, var_data) -> "Commits":
+        """A batch over effect columns already in the ABI's encoding (what am_generate_downstream /
+        am_update_objects_* wrote, unchanged).  transactions: [(dc, commit_time, snap, txid,
+        n_effects)], their effects consecutive in the columns."""
+        c = cls.__new__(cls)
+        c._init_columns(n_dc, [(int(d), int(ct), dict(sn), tx, int(ne)) for d, ct, sn, tx, ne in transactions],
+                        key, type_, eff_meta, p0, p1, var_off, var_data)
+        return c
+
+    def _init_columns(self, n_dc, txs, key, typ, meta, p0, p1, var_off, var):
+        if not 1 <= n_dc <= abi.AM_MAX_DC:
+            raise ValueError("n_dc out of range")
+        nt = len(txs)
+        self.n_dc, self.n_tx = n_dc, nt
+        self.dc = np.asarray([d for d, _, _, _, _ in txs] or [0], np.uint8)
+        self.commit_time = np.asarray([ct for _, ct, _, _, _ in txs] or [0], U64)
+        self.snap_vc = np.zeros((max(nt, 1), n_dc), U64)
+        self.snap_pres = np.zeros(max(nt, 1), np.uint32)
+        for i, (_, _, sn, _, _) in enumerate(txs):
+            for d, t in sn.items():
+                self.snap_vc[i, d] = t
+            self.snap_pres[i] = _pres(sn)
+        # (a transaction without effects leaves no op: it decides neither column)
+        self.has_pres = any(ne and int(p) != (1 << n_dc) - 1 for p, (_, _, _, _, ne) in zip(self.snap_pres, txs))
+        self.has_txid = any(ne and tx is not None for _, _, _, tx, ne in txs)
+        self.txid = np.asarray([0 if tx is None else int(tx) for _, _, _, tx, _ in txs] or [0], U64)
+        self.eff_off = np.zeros(nt + 1, U64)
+        self.eff_off[1:] = np.cumsum([ne for _, _, _, _, ne in txs], dtype=U64) if nt else []
+        n = int(self.eff_off[-1])
+        self.n_eff = n
+        c = lambda a, dt: np.ascontiguousarray(a if len(a) else [0], dt)  # noqa: E731
+        self.key, self.type, self.eff_meta = c(key, U64), c(typ, np.uint8), c(meta, np.uint8)
+        self.p0, self.p1 = c(p0, U64), c(p1, U64)
+        self.var_off = np.ascontiguousarray(var_off, U64)
+        self.n_var = int(self.var_off[n]) if len(self.var_off) > n else 0
+        self.var_data = c(var, U64)
+        self.has_var = True  # as_struct(var=False) drops the columns (no effect has variable words)
+        if len(self.key) < n or len(self.var_off) != n + 1:
+            raise ValueError("effect columns shorter than the transactions' effect counts")
+
+    def as_struct(self) -> abi.am_commits:
+        s = abi.am_commits()
+        s.n_tx, s.n_eff, s.n_var = self.n_tx, self.n_eff, self.n_var if self.has_var else 0
+        p = lambda a: a.ctypes.data  # noqa: E731
+        s.dc, s.commit_time, s.snap_vc = p(self.dc), p(self.commit_time), p(self.snap_vc)
+        s.snap_pres = p(self.snap_pres) if self.has_pres else None
+        s.txid = p(self.txid) if self.has_txid else None
+        s.eff_off, s.key, s.type, s.eff_meta = p(self.eff_off), p(self.key), p(self.type), p(self.eff_meta)
+        s.p0, s.p1 = p(self.p0), p(self.p1)
+        s.var_off = p(self.var_off) if self.has_var else None
+        s.var_data = p(self.var_data) if self.has_var else None
+        self._struct = s
+        return s
+
+    def effect(self, q: int) -> Tuple[int, int, int, List[int]]:
+        """Batch effect q decoded from the columns: (meta, p0, p1, var words)."""
+        return (int(self.eff_meta[q]), int(self.p0[q]), int(self.p1[q]),
+                [int(w) for w in self.var_data[int(self.var_off[q]):int(self.var_off[q + 1])]])
+
+    def ops_by_key(self) -> Dict[int, List[Op]]:
+        """The batch as the ops update_materializer/3 inserts, per key in commit order (decoded from
+        the columns): what Vnode.insert / HostLog take for the same batch."""
+        out: Dict[int, List[Op]] = {}
+        for t in range(self.n_tx):
+            snap = {d: int(self.snap_vc[t, d]) for d in range(self.n_dc) if (int(self.snap_pres[t]) >> d) & 1}
+            for q in range(int(self.eff_off[t]), int(self.eff_off[t + 1])):
+                meta, a, b, words = self.effect(q)
+                bad = bool(meta & abi.AM_META_BAD)
+                ty = int(self.type[q])
+                out.setdefault(int(self.key[q]), []).append(
+                    Op(ty, int(self.dc[t]), int(self.commit_time[t]), snap,
+                       None if bad else decode_effect(ty, meta, a, b, words),
+                       int(self.txid[t]) if self.has_txid else None, bad=bad))
+        return out
+
+    def reference_log(self) -> Dict[str, Any]:
+        """A numpy restatement of am_commit_build's output: keys (distinct, ascending), the CSR
+        columns over them and src.  A key's ops are ordered by (transaction, effect in the
+        transaction) -- a stable sort by key; op_meta = the transaction's dc | the effect's kind and
+        AM_META_BAD bits; key_type = the type of the key's first op; key_flags =
+        AM_KEY_MIXED_TYPES when the key's ops disagree."""
+        n, nt, nd = self.n_eff, self.n_tx, self.n_dc
+        tx_of = np.repeat(np.arange(nt, dtype=np.int64), np.diff(self.eff_off.astype(np.int64))) if nt else \
+            np.zeros(0, np.int64)
+        key = self.key[:n]
+        order = np.argsort(key, kind="stable")
+        ks = key[order]
+        head = np.ones(n, bool)
+        head[1:] = ks[1:] != ks[:-1]
+        kidx = np.cumsum(head) - 1
+        types = self.type[:n][order]
+        key_type = types[head]
+        key_flags = np.zeros(int(head.sum()), np.uint8)
+        key_flags[kidx[types != key_type[kidx]]] = abi.AM_KEY_MIXED_TYPES
+        tx = tx_of[order]
+        vo = self.var_off.astype(np.int64) if self.has_var else np.zeros(n + 1, np.int64)
+        lens = (vo[1:] - vo[:-1])[order]
+        out_vo = np.zeros(n + 1, U64)
+        out_vo[1:] = np.cumsum(lens, dtype=U64)
+        words = [self.var_data[vo[s]:vo[s + 1]] for s in order]
+        return {
+            "keys": ks[head].astype(U64),
+            "key_off": np.concatenate([np.flatnonzero(head), [n]]).astype(U64),
+            "key_type": key_type.astype(np.uint8), "key_flags": key_flags,
+            "op_meta": ((self.dc[:nt][tx] & 0x1F) | (self.eff_meta[:n][order] & 0xE0)).astype(np.uint8),
+            "commit_time": self.commit_time[:nt][tx].astype(U64),
+            "snap_vc": np.ascontiguousarray(self.snap_vc[:nt][tx].T.reshape(nd, n), U64),
+            "snap_pres": self.snap_pres[:nt][tx].astype(np.uint32) if self.has_pres else None,
+            "op_txid": self.txid[:nt][tx].astype(U64) if self.has_txid else None,
+            "p0": self.p0[:n][order].astype(U64), "p1": self.p1[:n][order].astype(U64),
+            "var_off": out_vo,
+            "var_data": np.concatenate(words + [np.zeros(0, U64)]).astype(U64),
+            "src": order.astype(np.uint32),
+        }

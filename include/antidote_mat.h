@@ -37,6 +37,9 @@
  *   am_vnode_insert_host    one partition's materializer_vnode state: op_insert_gc/3 with
  *   am_vnode_read_host      its write-triggered GC read (src/materializer_vnode.erl:622-647),
  *                           internal_read/7 with ShouldGC (:371-376), load_ops/2 (:312-319)
+ *   am_vnode_commit_host    clocksi_vnode:commit/5 -> update_materializer/3 (src/clocksi_vnode.erl:
+ *   am_commit_build         499-531, 634-657): a batch of committed transactions' effects, the op log
+ *                           over the touched keys built on the device
  *   am_read_objects_submit  clocksi_interactive_coord's read_objects fan-out over a GPU's
  *                           partitions (src/clocksi_interactive_coord.erl:732-747,
  *                           src/clocksi_readitem_server.erl:217-228) as one async batch
@@ -746,6 +749,77 @@ int am_update_objects_host(am_vnode *v, uint32_t n_parts, const uint64_t *part_k
 int am_update_objects_submit(am_vnode *v, uint32_t n_parts, const uint64_t *part_key_base, const uint32_t *part,
                              const am_read_batch *host_batch, const uint64_t *set_off, const am_writeset *host_ws,
                              const am_updates *host_up, am_effects *host_eff, int32_t *out_status, am_ticket **out);
+
+/* ---- commit on the device (am_commit.hip) ----
+ * clocksi_vnode:commit/5 -> update_materializer/3 (src/clocksi_vnode.erl:499-531, 634-657) stamps
+ * every effect of a transaction with {DcId, TxCommitTime}, its vec_snapshot_time and its TxId and
+ * hands it to materializer_vnode:update/2 -> op_insert_gc/3; inter_dc_dep_vnode does the same for a
+ * remote transaction under its own commit DC (src/inter_dc_dep_vnode.erl:150-152).  A batch of
+ * committed transactions goes in as it is -- one row per transaction, one row per effect in
+ * am_effects' / am_writeset's columns, `key` where the write set has `row` -- and the device turns
+ * it into the CSR op log over the touched keys that am_store_apply takes as dev_new. */
+typedef struct am_commits {      /* committed transactions, in the order the vnode commits them */
+  uint64_t n_tx, n_eff, n_var;
+  const uint8_t  *dc;            /* [n_tx] commit DC index (own DC, or a remote txn's origin)   */
+  const uint64_t *commit_time;   /* [n_tx]                                                       */
+  const uint64_t *snap_vc;       /* [n_tx][n_dc] vec_snapshot_time, transaction-major            */
+  const uint32_t *snap_pres;     /* [n_tx] or NULL = every DC present                            */
+  const uint64_t *txid;          /* [n_tx] am_txid ids, or NULL                                  */
+  const uint64_t *eff_off;       /* [n_tx+1] transaction t's effects, oldest first               */
+  const uint64_t *key;           /* [n_eff] vnode key                                            */
+  const uint8_t  *type;          /* [n_eff] am_type                                              */
+  const uint8_t  *eff_meta; const uint64_t *p0, *p1;   /* [n_eff] as am_effects / am_writeset    */
+  const uint64_t *var_off, *var_data;                  /* [n_eff+1] or NULL, [n_var]             */
+} am_commits;
+/* The device buffers am_commit_build writes, supplied by the caller (n_eff and n_var are known on
+ * the host before the call): cap_ops >= n_eff, cap_var >= n_var, snap_stride >= cap_ops. */
+typedef struct am_commit_log {
+  uint64_t cap_ops, cap_var, snap_stride;
+  uint64_t *keys;                /* [cap_ops] the distinct keys, ascending                       */
+  uint64_t *key_off;             /* [cap_ops+1]                                                  */
+  uint8_t  *key_type, *key_flags;/* [cap_ops]                                                    */
+  uint8_t  *op_meta;             /* [cap_ops]                                                    */
+  uint64_t *commit_time;         /* [cap_ops]                                                    */
+  uint64_t *snap_vc;             /* [n_dc][snap_stride] DC-major                                 */
+  uint32_t *snap_pres;           /* [cap_ops]; written when the batch has snap_pres              */
+  uint64_t *op_txid;             /* [cap_ops]; written when the batch has txid                   */
+  uint64_t *p0, *p1;             /* [cap_ops]                                                    */
+  uint64_t *var_off;             /* [cap_ops+1]                                                  */
+  uint64_t *var_data;            /* [cap_var]                                                    */
+  uint32_t *src;                 /* [cap_ops] the batch effect index of each output op           */
+} am_commit_log;
+/* *bad of am_commit_build: why the batch is invalid */
+#define AM_COMMIT_BAD_DC 0x1u       /* a transaction's dc >= n_dc                                 */
+#define AM_COMMIT_BAD_EFF_OFF 0x2u  /* eff_off decreasing, not starting at 0 or not ending at n_eff */
+#define AM_COMMIT_BAD_VAR_OFF 0x4u  /* var_off decreasing or beyond n_var                         */
+#define AM_COMMIT_BAD_TYPE 0x8u     /* an unknown am_type                                         */
+#define AM_COMMIT_BAD_KEY 0x10u     /* a key with bits at or above key_bits set                   */
+/* Device pointers in dev_commits and out (the structs themselves live in host memory); runs on the
+ * context stream with ONE readback, a status block holding *n_touched and *bad.  On AM_OK
+ * *out_log is the am_op_log over out's buffers (n_keys = *n_touched, n_ops = n_eff; snap_pres /
+ * op_txid NULL when the batch has none), ready as am_store_apply's dev_new with out->keys:
+ *   order      a key's ops by (transaction index, effect index in the transaction): a stable sort
+ *              by key alone (update_materializer's lists:reverse + foldl across serial commits);
+ *              two effects of one transaction on one key stay two ops, in order
+ *   op_meta    the transaction's dc in the DC bits | the effect's kind and AM_META_BAD bits;
+ *              commit_time, snap_pres, op_txid broadcast from the transaction; snap_vc transposed
+ *   key_type   the type of the key's first op in the batch; key_flags = AM_KEY_MIXED_TYPES when
+ *              the key's ops in the batch disagree
+ *   src[q]     the batch effect index of output op q
+ * key_bits: the radix sort covers the low key_bits bits of the keys (1..64, the bits the batch's
+ * largest key needs; 64 always works).  AM_ERR_INVALID (*bad says why, nothing in out is to be
+ * used): dc >= n_dc, eff_off not non-decreasing from 0 to n_eff, var_off decreasing or beyond
+ * n_var, an unknown type, a key above key_bits, n_eff >= 2^32, capacities below the batch.
+ * n_tx == 0 or n_eff == 0: AM_OK with *n_touched = 0. */
+int am_commit_build(am_ctx *ctx, uint32_t n_dc, const am_commits *dev_commits, uint32_t key_bits,
+                    const am_commit_log *out, am_op_log *out_log, uint64_t *n_touched, uint32_t *bad /* or NULL */);
+/* op_insert_gc/3 for every effect of a host batch, as am_vnode_insert_host does for the same ops
+ * given as a host log (ids OpCounter+1.., the write-triggered GC reads with the trigger op's
+ * snapshot_time, ListLen resizing, in-place apply or one rebuild, growth of the key space to the
+ * batch's largest key + 1, am_vnode_stats), at O(batch) on the host: the batch is uploaded,
+ * am_commit_build runs, and only the touched keys, their counts and src come back to plan the GC
+ * rounds.  An invalid batch returns AM_ERR_INVALID and leaves the vnode as it was.  Blocks. */
+int am_vnode_commit_host(am_vnode *v, const am_commits *host_commits);
 
 /* ---- op-cache ingestion + garbage collection ----
  * Builds a new store from `st` (st is unchanged; destroy it when no read uses it):
