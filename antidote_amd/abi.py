@@ -260,6 +260,15 @@ SIGNATURES = [
     ("am_commit_build", c_int, [c_void_p, c_uint32, POINTER(am_commits), c_uint32, POINTER(am_commit_log),
                                 POINTER(am_op_log), POINTER(c_uint64), POINTER(c_uint32)]),
     ("am_vnode_commit_host", c_int, [c_void_p, POINTER(am_commits)]),
+    ("am_plog_create", c_int, [c_void_p, c_uint32, c_uint64, c_uint64, c_uint64, POINTER(c_void_p)]),
+    ("am_plog_destroy", c_int, [c_void_p]),
+    ("am_plog_append_host", c_int, [c_void_p, POINTER(am_commits)]),
+    ("am_plog_size", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("am_plog_key_ops", c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, POINTER(c_uint64)]),
+    ("am_plog_read", c_int, [c_void_p, c_void_p, POINTER(am_read_batch), c_void_p, POINTER(am_read_result)]),
+    ("am_plog_read_host", c_int, [c_void_p, c_void_p, POINTER(am_read_batch), c_void_p, POINTER(am_read_result)]),
+    ("am_vnode_create_logged", c_int, [c_void_p, c_uint32, c_uint64, POINTER(c_void_p)]),
+    ("am_vnode_log", c_int, [c_void_p, POINTER(c_void_p)]),
     ("am_codec_create", c_int, [POINTER(c_void_p)]),
     ("am_codec_destroy", c_int, [c_void_p]),
     ("am_codec_intern", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),

@@ -252,6 +252,24 @@ int am_commit_slice(am_ctx *c, const am_op_log &B, uint64_t m, const uint64_t *i
 int am_commit_spread(am_ctx *c, const am_op_log &T, const uint64_t *keys, uint64_t n_keys, uint64_t *off, uint8_t *type,
                      uint8_t *flags);
 
+// The partition log's internals (am_plog.hip).  am_plog_append_built: a batch am_commit_build
+// accepted (dev_cm; src / bkey_off / m its output, max_key the batch's largest key) behind the log,
+// stream-ordered and without a readback.  am_plog_launch_read: am_plog_read without the argument
+// checks; survivors (device [n] or null) receives each read's op count.
+int am_plog_append_built(am_plog *g, const am_commits *dev_cm, const uint32_t *src, const uint64_t *bkey_off, uint64_t m,
+                         uint64_t max_key);
+int am_plog_launch_read(am_ctx *c, const am_plog *g, const am_read_batch *B, const uint64_t *hor, am_read_result *R,
+                        uint64_t *survivors);
+// a codec relabel map (host arrays) applied to the log's label words, by each effect's type
+int am_plog_relabel(am_plog *g, const uint64_t *old_labels, const uint64_t *new_labels, uint64_t n);
+// am_snapcache_read_gc with the partition's log (am_snapcache.hip): the reads no cached snapshot
+// serves (AM_ERR_COLD_PATH without a log) are read from plog -- read r among its first horizon[r]
+// transactions (device [n], or null = the whole log) -- and stored as materialize_snapshot/7 stores
+// a response that is not the newest snapshot: iff ShouldGC.  plog null: am_snapcache_read_gc.
+int am_snapcache_read_gc_log(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const am_read_batch *B,
+                             const uint8_t *should_gc, am_read_result *R, uint8_t *gc_mask, uint64_t *thr_vc,
+                             uint32_t *thr_pres, const am_plog *plog, const uint64_t *horizon);
+
 // host arrays -> one device arena (stream-ordered copies); the host sources outlive the call
 struct am_stage {
   struct Item {

@@ -16,6 +16,9 @@
 //                  (:515-563): at SNAPSHOT_THRESHOLD entries, or on ShouldGC, the dict
 //                  keeps its newest SNAPSHOT_MIN entries and the key's prune threshold
 //                  (vectorclock:min over them) is emitted for prune_ops (am_store_update)
+//   k_sc_cold_*    with the partition's log (am_snapcache_read_gc_log): the reads k_sc_select
+//                  sent to the log cold path, compacted, read from the log (am_plog.hip) and
+//                  written in place before k_sc_store, which stores them iff ShouldGC
 //   k_sc_release   frees the key claims
 // Layout: per key a fixed array of CAP entries, newest first (clock [n_dc] + presence,
 // last_op_id, value), entry-major: field[e][key] (clocks [e][d][key]), so a batch's reads of
@@ -65,7 +68,8 @@ constexpr uint32_t SMIN = AM_SNAPSHOT_MIN;
 constexpr uint32_t MIN_OP_STORE_SS = AM_MIN_OP_STORE_SS;
 constexpr uint8_t ABSENT = 0xFF;
 // per-read selection codes (scratch)
-enum : uint8_t { SEL_CACHED = 0, SEL_NEW_DICT = 1, SEL_COLD = 2, SEL_DUP = 3, SEL_BAD = 4 };
+// (SEL_COLD_DONE: a cold read whose result row the device log has written, am_plog.hip)
+enum : uint8_t { SEL_CACHED = 0, SEL_NEW_DICT = 1, SEL_COLD = 2, SEL_DUP = 3, SEL_BAD = 4, SEL_COLD_DONE = 5 };
 
 struct ScView {  // kernel-side copy of the cache pointers
   uint32_t n_dc;
@@ -93,6 +97,7 @@ struct ScSel {
   int64_t *base_last_op, *v0;
   uint64_t *cp_dst;  // k_sc_store -> k_sc_copy: the stored snapshot's value words go to pool
   uint32_t *cp_len;  //   words [cp_dst, cp_dst + cp_len) from the read's result CSR (0: none)
+  uint64_t *cold_ops;  // [n] number_of_ops of a SEL_COLD_DONE read's log response (null without a log)
 };
 // prune thresholds emitted by snapshot_insert_gc (optional)
 struct ScGc {
@@ -261,7 +266,10 @@ __global__ void __launch_bounds__(256) k_sc_store(ScView C, am_op_log L, am_read
     }
     // materialize_snapshot/7: number_of_ops == 0 returns the base; errors and
     // CommitTime == ignore return without caching
-    act = act && R.status[r] == AM_OK && am_kend(L, key) != L.key_off[key] && !R.last_ct_ignore[r];
+    // (a read served from the log: number_of_ops is its survivor count, and the response is never
+    // the newest snapshot, so it is stored iff ShouldGC)
+    const bool has_ops = code == SEL_COLD_DONE ? S.cold_ops[r] != 0 : am_kend(L, key) != L.key_off[key];
+    act = act && R.status[r] == AM_OK && has_ops && !R.last_ct_ignore[r];
     const bool sg = act && should_gc && should_gc[r];
     act = act && ((R.is_new_ss[r] && S.newest[r] && R.count[r] >= MIN_OP_STORE_SS) || sg);
     // internal_store_ss/4: ShouldInsert = NewLastOp - first.last_op_id >= MIN_OP_STORE_SS
@@ -349,6 +357,80 @@ __global__ void k_sc_copy(ScView C, am_read_result R, ScSel S, uint64_t n) {
       C.pool_a[dst + i] = R.value.set_a[src + i], C.pool_b[dst + i] = R.value.set_b[src + i];
       C.pool_g[dst + i] = ~0u;  // no group hint
     }
+  }
+}
+
+// ---- the SEL_COLD reads of a batch, served from the device log (am_plog.hip) ----
+// flag[r] = read r went cold, capf[r] = its set capacity ([n+1], entry n = 0): their exclusive
+// scans are the read's index in the cold sub-batch and its set_off there
+__global__ void k_sc_cold_mark(const uint8_t *code, const uint64_t *set_off, uint64_t n, uint64_t *flag, uint64_t *capf) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += (uint64_t)gridDim.x * blockDim.x) {
+    const bool cold = r < n && code[r] == SEL_COLD;
+    flag[r] = cold ? 1 : 0;
+    capf[r] = cold && set_off ? set_off[r + 1] - set_off[r] : 0;
+  }
+}
+
+// the cold sub-batch: its reads' columns (one clock per read) and set_off
+struct ScCold {
+  uint64_t nc;
+  const uint64_t *pos, *coff;  // [n+1] the scans above
+  uint64_t *key, *read_vc, *txid, *hor, *set_off;
+  uint32_t *read_pres;
+  uint8_t *type, *txid_valid;
+};
+
+__global__ void k_sc_cold_gather(am_read_batch B, const uint8_t *code, const uint64_t *hor, uint32_t nd, ScCold X) {
+  const uint64_t n = B.n_reads;
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += (uint64_t)gridDim.x * blockDim.x) {
+    if (r == n) {
+      X.set_off[X.nc] = X.coff[n];
+      continue;
+    }
+    if (code[r] != SEL_COLD) continue;
+    const uint64_t i = X.pos[r];
+    const uint64_t ci = B.per_read_clock ? r : 0, cs = B.per_read_clock ? n : 1;
+    X.key[i] = B.key[r];
+    X.type[i] = B.type[r];
+    for (uint32_t d = 0; d < nd; ++d) X.read_vc[(uint64_t)d * X.nc + i] = B.read_vc[(uint64_t)d * cs + ci];
+    X.read_pres[i] = B.read_pres[ci];
+    X.txid[i] = B.txid ? B.txid[r] : 0;
+    X.txid_valid[i] = B.txid ? (B.txid_valid ? B.txid_valid[r] : 1) : 0;
+    X.hor[i] = hor ? hor[r] : ~0ull;
+    X.set_off[i] = X.coff[r];
+  }
+}
+
+// the sub-batch's result rows (Q, over nc reads) written in place into the batch's (R); the read
+// becomes SEL_COLD_DONE with its survivor count, never the newest snapshot, and not teed
+__global__ void k_sc_cold_scatter(am_read_result R, am_read_result Q, uint64_t n, uint32_t nd, ScCold X, const uint64_t *surv,
+                                  ScSel S, uint8_t *teed) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+    if (S.code[r] != SEL_COLD) continue;
+    const uint64_t i = X.pos[r];
+    R.status[r] = Q.status[i];
+    R.new_last_op[r] = Q.new_last_op[i];
+    for (uint32_t d = 0; d < nd; ++d) R.last_ct[(uint64_t)d * n + r] = Q.last_ct[(uint64_t)d * X.nc + i];
+    R.last_ct_pres[r] = Q.last_ct_pres[i];
+    R.last_ct_ignore[r] = Q.last_ct_ignore[i];
+    R.is_new_ss[r] = Q.is_new_ss[i];
+    R.count[r] = Q.count[i];
+    R.flags[r] = Q.flags[i];
+    if (R.value.v0) R.value.v0[r] = Q.value.v0[i];
+    if (R.value.v1) R.value.v1[r] = Q.value.v1[i];
+    if (R.value.vflag) R.value.vflag[r] = Q.value.vflag[i];
+    if (R.value.set_off && R.value.set_len) {
+      const uint64_t cap = R.value.set_off[r + 1] - R.value.set_off[r];
+      const uint32_t len = Q.value.set_len[i];
+      R.value.set_len[r] = len;
+      const uint64_t dst = R.value.set_off[r], src = X.set_off[i];
+      for (uint64_t w = 0; w < len && w < cap; ++w)
+        R.value.set_a[dst + w] = Q.value.set_a[src + w], R.value.set_b[dst + w] = Q.value.set_b[src + w];
+    }
+    S.cold_ops[r] = surv[i];
+    S.newest[r] = 0;
+    S.code[r] = SEL_COLD_DONE;
+    if (teed) teed[r] = 0;
   }
 }
 
@@ -675,9 +757,95 @@ int am_snapcache_destroy(am_snapcache *c) {
   return AM_OK;
 }
 
-int am_snapcache_read_gc(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const am_read_batch *B,
-                         const uint8_t *should_gc, am_read_result *R, uint8_t *gc_mask, uint64_t *thr_vc,
-                         uint32_t *thr_pres) {
+}  // extern "C"
+
+namespace {
+
+// get_from_snapshot_log/3 for the batch's SEL_COLD reads (src/materializer_vnode.erl:400-403,
+// 415-419): compacted into a sub-batch, read from the device log (am_plog.hip) and their result
+// rows written in place, before k_sc_store.  One readback: the number of cold reads and their set
+// capacity (a batch without cold reads ends there).  The sub-batch lives in an am_dev_alloc block:
+// the nested am_launch_materialize takes the context's scratch slots.
+int cold_reads(am_ctx *ctx, const am_plog *plog, const uint64_t *hor, uint32_t nd, const am_read_batch *B, am_read_result *R,
+               ScSel S, uint8_t *teed) {
+  const uint64_t n = B->n_reads;
+  size_t scan_b = 0;
+  uint64_t *nul = nullptr;
+  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, nul, nul, (int)(n + 1), ctx->stream) != hipSuccess) return AM_ERR_HIP;
+  struct Cols {
+    size_t total = 0;
+    size_t add(size_t bytes) {
+      const size_t o = total;
+      total += (bytes + 255) & ~(size_t)255;
+      return o;
+    }
+  } mc;
+  const size_t c8 = (n + 1) * 8;
+  const size_t m_flag = mc.add(c8), m_capf = mc.add(c8), m_pos = mc.add(c8), m_coff = mc.add(c8), m_tot = mc.add(16);
+  const size_t m_tmp = mc.add(scan_b);
+  char *M = nullptr, *X = nullptr;
+  if (int rc = am_dev_alloc(ctx, mc.total, (void **)&M)) return rc;
+  auto done = [&](int rc) {
+    if (X) am_dev_release(ctx, X);
+    am_dev_release(ctx, M);
+    return rc;
+  };
+  uint64_t *flag = (uint64_t *)(M + m_flag), *capf = (uint64_t *)(M + m_capf), *pos = (uint64_t *)(M + m_pos);
+  uint64_t *coff = (uint64_t *)(M + m_coff), *tot = (uint64_t *)(M + m_tot);
+  hipLaunchKernelGGL(k_sc_cold_mark, dim3(grid(n + 1)), dim3(256), 0, ctx->stream, S.code, R->value.set_off, n, flag, capf);
+  size_t tb = scan_b;
+  bool ok = hipcub::DeviceScan::ExclusiveSum(M + m_tmp, tb, flag, pos, (int)(n + 1), ctx->stream) == hipSuccess;
+  tb = scan_b;
+  ok = ok && hipcub::DeviceScan::ExclusiveSum(M + m_tmp, tb, capf, coff, (int)(n + 1), ctx->stream) == hipSuccess;
+  ok = ok && hipMemcpyAsync(tot, pos + n, 8, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess &&
+       hipMemcpyAsync(tot + 1, coff + n, 8, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess;
+  if (!ok || hipGetLastError() != hipSuccess) return done(AM_ERR_HIP);
+  uint64_t h[2] = {0, 0};
+  if (int rc = am_ctx_fetch(ctx, tot, 2, h)) return done(rc);
+  const uint64_t nc = h[0], words = h[1];
+  if (nc == 0) return done(AM_OK);
+  Cols xc;
+  const size_t x_key = xc.add(nc * 8), x_vc = xc.add(nc * nd * 8), x_tx = xc.add(nc * 8), x_hor = xc.add(nc * 8);
+  const size_t x_so = xc.add((nc + 1) * 8), x_rp = xc.add(nc * 4), x_ty = xc.add(nc), x_tv = xc.add(nc), x_sv = xc.add(nc * 8);
+  const size_t q_st = xc.add(nc * 4), q_nlo = xc.add(nc * 8), q_ct = xc.add(nc * nd * 8), q_cp = xc.add(nc * 4);
+  const size_t q_ci = xc.add(nc), q_ns = xc.add(nc), q_cn = xc.add(nc * 4), q_fl = xc.add(nc), q_v0 = xc.add(nc * 8);
+  const size_t q_v1 = xc.add(nc * 8), q_vf = xc.add(nc), q_sl = xc.add(nc * 4), q_sa = xc.add((words + 1) * 8);
+  const size_t q_sb = xc.add((words + 1) * 8);
+  if (int rc = am_dev_alloc(ctx, xc.total, (void **)&X)) return done(rc);
+  if (hipMemsetAsync(X, 0, xc.total, ctx->stream) != hipSuccess) return done(AM_ERR_HIP);
+  ScCold C{};
+  C.nc = nc, C.pos = pos, C.coff = coff;
+  C.key = (uint64_t *)(X + x_key), C.read_vc = (uint64_t *)(X + x_vc), C.txid = (uint64_t *)(X + x_tx);
+  C.hor = (uint64_t *)(X + x_hor), C.set_off = (uint64_t *)(X + x_so), C.read_pres = (uint32_t *)(X + x_rp);
+  C.type = (uint8_t *)(X + x_ty), C.txid_valid = (uint8_t *)(X + x_tv);
+  hipLaunchKernelGGL(k_sc_cold_gather, dim3(grid(n + 1)), dim3(256), 0, ctx->stream, *B, (const uint8_t *)S.code, hor, nd, C);
+  if (hipGetLastError() != hipSuccess) return done(AM_ERR_HIP);
+  am_read_batch sb{};
+  sb.n_reads = nc, sb.per_read_clock = 1, sb.type_hint = B->type_hint;
+  sb.key = C.key, sb.type = C.type, sb.read_vc = C.read_vc, sb.read_pres = C.read_pres;
+  if (B->txid) sb.txid = C.txid, sb.txid_valid = C.txid_valid;
+  am_read_result Q{};
+  Q.status = (int32_t *)(X + q_st), Q.new_last_op = (int64_t *)(X + q_nlo), Q.last_ct = (uint64_t *)(X + q_ct);
+  Q.last_ct_pres = (uint32_t *)(X + q_cp), Q.last_ct_ignore = (uint8_t *)(X + q_ci), Q.is_new_ss = (uint8_t *)(X + q_ns);
+  Q.count = (uint32_t *)(X + q_cn), Q.flags = (uint8_t *)(X + q_fl);
+  Q.value.v0 = (int64_t *)(X + q_v0), Q.value.v1 = (uint64_t *)(X + q_v1), Q.value.vflag = (uint8_t *)(X + q_vf);
+  if (R->value.set_off && R->value.set_len && R->value.set_a && R->value.set_b) {
+    Q.value.set_off = C.set_off, Q.value.set_len = (uint32_t *)(X + q_sl);
+    Q.value.set_a = (uint64_t *)(X + q_sa), Q.value.set_b = (uint64_t *)(X + q_sb);
+  }
+  uint64_t *surv = (uint64_t *)(X + x_sv);
+  if (int rc = am_plog_launch_read(ctx, plog, &sb, C.hor, &Q, surv)) return done(rc);
+  hipLaunchKernelGGL(k_sc_cold_scatter, dim3(grid(n)), dim3(256), 0, ctx->stream, *R, Q, n, nd, C, (const uint64_t *)surv, S,
+                     teed);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return done(AM_ERR_HIP);
+  return done(AM_OK);
+}
+
+}  // namespace
+
+int am_snapcache_read_gc_log(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const am_read_batch *B,
+                             const uint8_t *should_gc, am_read_result *R, uint8_t *gc_mask, uint64_t *thr_vc,
+                             uint32_t *thr_pres, const am_plog *plog, const uint64_t *horizon) {
   if (!ctx || !c || !L || !B || !R || c->ctx != ctx) return AM_ERR_INVALID;
   AM_LOCK(ctx);
   if (L->n_dc != c->n_dc || L->n_keys != c->n_keys) {
@@ -717,7 +885,7 @@ int am_snapcache_read_gc(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const
   }
   // scratch: code, newest, base_ignore, vflag [n] u8 | base_pres, set_len [n] u32 |
   // base_last_op, v0, v1, set_off [n] u64 | base_vc [nd][n]
-  const size_t bytes = n * (4 + 8 + 4 * 8 + (size_t)nd * 8 + 13) + 4096;
+  const size_t bytes = n * (4 + 8 + 4 * 8 + (size_t)nd * 8 + 13 + (plog ? 8 : 0)) + 4096 + 256;
   void *scr = nullptr;
   int rc = am_ctx_scratch(ctx, AM_SCR_SNAP, bytes, &scr);
   if (rc) return rc;
@@ -742,6 +910,7 @@ int am_snapcache_read_gc(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const
   S.base_ignore = (uint8_t *)take(n);
   S.vflag = (uint8_t *)take(n);
   uint8_t *teed = (uint8_t *)take(n);
+  S.cold_ops = plog ? (uint64_t *)take(n * 8) : nullptr;
   const ScView V = view(c);
   hipLaunchKernelGGL(k_sc_claim, dim3(grid(n)), dim3(256), 0, ctx->stream, V, *B);
   hipLaunchKernelGGL(k_sc_select, dim3(grid(n)), dim3(256), 0, ctx->stream, V, *B, S);
@@ -771,6 +940,7 @@ int am_snapcache_read_gc(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const
     rc = am_launch_materialize(ctx, L, &db, R);
     ctx->grp_hint_in = nullptr;
     ctx->tee_a = ctx->tee_b = nullptr, ctx->tee_g = nullptr, ctx->tee_done = nullptr, ctx->tee_shift = 0;
+    if (rc == AM_OK && plog) rc = cold_reads(ctx, plog, horizon, nd, B, R, S, tee ? teed : nullptr);
     if (rc == AM_OK) {
       const ScGc G{gc_mask, thr_vc, thr_pres};
       hipLaunchKernelGGL(k_sc_store, dim3(grid(n)), dim3(256), 0, ctx->stream, V, *L, *B, *R, S, should_gc, G, used,
@@ -785,6 +955,14 @@ int am_snapcache_read_gc(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const
   hipLaunchKernelGGL(k_sc_release, dim3(grid(n)), dim3(256), 0, ctx->stream, V, *B);  // every exit path
   AM_HIP(hipGetLastError());
   return rc;
+}
+
+extern "C" {
+
+int am_snapcache_read_gc(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const am_read_batch *B,
+                         const uint8_t *should_gc, am_read_result *R, uint8_t *gc_mask, uint64_t *thr_vc,
+                         uint32_t *thr_pres) {
+  return am_snapcache_read_gc_log(ctx, c, L, B, should_gc, R, gc_mask, thr_vc, thr_pres, nullptr, nullptr);
 }
 
 int am_snapcache_read(am_ctx *ctx, am_snapcache *c, const am_op_log *L, const am_read_batch *B, am_read_result *R) {

@@ -56,6 +56,11 @@ struct am_vnode {
   uint64_t rebuilds = 0;        // whole-store rebuilds (a key outgrew its room) ...
   uint64_t applies = 0;         // ... and in-place applies of touched keys
   std::atomic<int> in_flight{0};  // am_read_objects_submit tickets not yet finished
+  // am_vnode_create_logged: the partition's log (am_plog.hip).  Every commit batch is appended to it
+  // before the materializer is updated, and the reads no cached snapshot serves are read from it
+  // (get_from_snapshot_log, src/materializer_vnode.erl:400-403) instead of ending as
+  // AM_ERR_COLD_PATH.  Null: a plain vnode.
+  am_plog *plog = nullptr;
 };
 
 namespace {
@@ -217,12 +222,17 @@ struct ReadArg {
   const uint64_t *host_set_off;  // the result's set capacities (host copy)
   const DownArg *down;         // the updates to turn into effects, or null
   uint64_t n_reads;
+  bool has_hor;                // the staged extra block holds the reads' log horizons behind should_gc
 };
+// should_gc [n] padded to u64 words, then (a logged vnode's GC reads) the horizons [n]
+size_t hor_offset(uint64_t n) { return (n + 7) & ~(size_t)7; }
 int run_round(void *arg, const am_read_batch *db, am_read_result *dr, const void *extra_dev) {
   const ReadArg *a = static_cast<ReadArg *>(arg);
   am_vnode *v = a->v;
-  int rc = am_snapcache_read_gc(v->ctx, v->sc, &v->st->dev, db, (const uint8_t *)extra_dev, dr, v->gc_mask, v->thr_vc,
-                                v->thr_pres);
+  const uint64_t *hor = a->has_hor ? (const uint64_t *)((const char *)extra_dev + hor_offset(a->n_reads)) : nullptr;
+  // (a logged vnode resolves its cold reads here, before the write set and the updates see the rows)
+  int rc = am_snapcache_read_gc_log(v->ctx, v->sc, &v->st->dev, db, (const uint8_t *)extra_dev, dr, v->gc_mask, v->thr_vc,
+                                    v->thr_pres, v->plog, hor);
   // apply_tx_updates_to_snapshot/4 on the device result, before it is copied back
   if (!rc && a->ws && a->ws->n_ws) rc = am_eager_apply_result(v->ctx, v->n_dc, a->ws, a->host_set_off, dr);
   // ... and Type:downstream/2 on the values, which stay on the device
@@ -233,11 +243,13 @@ int run_round(void *arg, const am_read_batch *db, am_read_result *dr, const void
 
 // one round of reads over distinct keys (host arrays), then the GCs they triggered
 int read_round(am_vnode *v, const am_read_batch *hb, const uint8_t *should_gc, am_read_result *hr,
-               const am_writeset *ws = nullptr, const DownArg *down = nullptr) {
+               const am_writeset *ws = nullptr, const DownArg *down = nullptr, const uint64_t *horizon = nullptr) {
   const uint64_t n = hb->n_reads;
-  ReadArg a{v, ws, hr->value.set_off, down, n};
-  std::vector<uint8_t> sg(n, 0);
+  const bool has_hor = v->plog && horizon;
+  ReadArg a{v, ws, hr->value.set_off, down, n, has_hor};
+  std::vector<uint8_t> sg(has_hor ? hor_offset(n) + n * 8 : n, 0);
   if (should_gc) std::copy(should_gc, should_gc + n, sg.begin());
+  if (has_hor) memcpy(sg.data() + hor_offset(n), horizon, n * 8);
   int rc = am_run_host_batch(v->ctx, v->st, hb, hr, sg.data(), sg.size(), run_round, &a, down != nullptr);
   if (rc) return rc;
   // the GC mask of the batch's keys only (keys past the vnode's are invalid reads)
@@ -267,6 +279,9 @@ struct OpSource {
   // op p's snapshot_time: its presence bits (every DC when the source has none) and entry d
   virtual uint32_t snap_pres(uint64_t p) const = 0;
   virtual uint64_t snap_vc(uint64_t p, uint64_t d) const = 0;
+  // the log horizon of op p's GC read on a logged vnode: its transaction's index + 1 -- the commit
+  // record is appended before the materializer is updated (src/clocksi_vnode.erl:517-519)
+  virtual uint64_t horizon(uint64_t) const { return ~0ull; }
   // the ops [beg_i, end_i) of source key srck_i onto vnode key keys_i: in place, or a whole-store
   // rebuild with the new ops when a key outgrows its room
   virtual int append(am_vnode *v, const std::vector<uint64_t> &keys, const std::vector<uint64_t> &srck,
@@ -432,8 +447,10 @@ int gc_reads(am_vnode *v, const OpSource &src, std::vector<uint64_t> keys, std::
     std::vector<uint8_t> type(n), sg(n, 1);
     std::vector<uint64_t> vc(nd * n);
     std::vector<uint32_t> rp(n);
+    std::vector<uint64_t> hor(n);
     for (uint64_t i = 0; i < n; ++i) {
       const uint64_t p = trig[i];
+      hor[i] = src.horizon(p);
       type[i] = v->type[keys[i]];
       rp[i] = src.snap_pres(p) & all;
       for (uint64_t d = 0; d < nd; ++d) vc[d * n + i] = ((rp[i] >> d) & 1u) ? src.snap_vc(p, d) : 0;
@@ -446,7 +463,7 @@ int gc_reads(am_vnode *v, const OpSource &src, std::vector<uint64_t> keys, std::
     b.read_vc = vc.data();
     b.read_pres = rp.data();
     HostResult hr(n, v->n_dc, cap);
-    int rc = read_round(v, &b, sg.data(), &hr.r);
+    int rc = read_round(v, &b, sg.data(), &hr.r, nullptr, nullptr, hor.data());
     if (rc) return rc;
     std::vector<uint64_t> again, again_t;
     for (uint64_t i = 0; i < n; ++i)
@@ -513,7 +530,9 @@ struct DevLogSource : OpSource {
   std::vector<uint32_t> src;      // the batch effect of every built op
   std::vector<uint32_t> tx_of;    // the transaction of every batch effect
   uint64_t nd;
+  uint64_t log_base = 0;          // a logged vnode: the log's transactions before this batch
   DevLogSource(const am_commits &h, uint64_t nd_) : hc(h), nd(nd_) {}
+  uint64_t horizon(uint64_t p) const override { return log_base + tx_of[src[p]] + 1; }
   uint8_t key_type(uint64_t srck) const override { return ktype[srck]; }
   uint32_t snap_pres(uint64_t p) const override { return hc.snap_pres ? hc.snap_pres[tx_of[src[p]]] : 0xFFFFFFFFu; }
   uint64_t snap_vc(uint64_t p, uint64_t d) const override { return hc.snap_vc[(uint64_t)tx_of[src[p]] * nd + d]; }
@@ -621,6 +640,7 @@ int am_vnode_destroy(am_vnode *v) {
   std::lock_guard<std::recursive_mutex> lk(c->mu);       // and every call in progress
   if (v->st) am_store_destroy(v->st);
   if (v->sc) am_snapcache_destroy(v->sc);
+  if (v->plog) am_plog_destroy(v->plog);
   if (v->gc_mask) am_dev_free(v->ctx, v->gc_mask);
   if (v->gc_flags) am_dev_free(v->ctx, v->gc_flags);
   if (v->thr_vc) am_dev_free(v->ctx, v->thr_vc);
@@ -629,9 +649,32 @@ int am_vnode_destroy(am_vnode *v) {
   return AM_OK;
 }
 
+int am_vnode_create_logged(am_ctx *ctx, uint32_t n_dc, uint64_t n_keys, am_vnode **out) {
+  if (!out) return AM_ERR_INVALID;
+  am_vnode *v = nullptr;
+  if (int rc = am_vnode_create(ctx, n_dc, n_keys, &v)) return rc;
+  if (int rc = am_plog_create(ctx, n_dc, 1024, 4096, 4096, &v->plog)) {
+    am_vnode_destroy(v);
+    return rc;
+  }
+  *out = v;
+  return AM_OK;
+}
+
+int am_vnode_log(am_vnode *v, am_plog **plog) {
+  if (!v || !plog) return AM_ERR_INVALID;
+  AM_LOCK(v->ctx);
+  *plog = v->plog;
+  return AM_OK;
+}
+
 int am_vnode_insert_host(am_vnode *v, const am_op_log *h) {
   if (!v) return AM_ERR_INVALID;
   AM_LOCK(v->ctx);
+  if (v->plog) {
+    am_set_error("am_vnode_insert_host: a logged vnode takes commit batches only (a per-key log has no commit order)");
+    return AM_ERR_UNSUPPORTED;
+  }
   if (!v || !h || h->n_keys < v->n_keys || h->n_dc != v->n_dc || !h->key_off || !h->key_type || !h->op_meta ||
       !h->commit_time || !h->p0 || (h->n_ops && !h->snap_vc)) {
     am_set_error("am_vnode_insert_host: the new ops must be a host log over (at least) the vnode's keys");
@@ -651,6 +694,7 @@ int am_vnode_commit_host(am_vnode *v, const am_commits *h) {
   if (!v || !h) return AM_ERR_INVALID;
   AM_LOCK(v->ctx);
   const uint64_t n = h->n_eff, nt = h->n_tx, nd = v->n_dc;
+  if (v->plog && nt && n == 0) return am_plog_append_host(v->plog, h);  // commit records without updates
   if (nt == 0 || n == 0) return n ? AM_ERR_INVALID : AM_OK;
   if (!h->dc || !h->commit_time || !h->snap_vc || !h->eff_off || !h->key || !h->type || !h->eff_meta || !h->p0 || !h->p1 ||
       (h->var_off && h->n_var && !h->var_data) || (n >> 32) || (nt >> 32)) {
@@ -703,6 +747,10 @@ int am_vnode_commit_host(am_vnode *v, const am_commits *h) {
   DevLogSource src(*h, nd);
   uint64_t m = 0;
   if (int rc = am_commit_build(v->ctx, v->n_dc, &dc, key_bits, &o, &src.built, &m, nullptr)) return done(rc);
+  if (v->plog) {  // append_commit before update_materializer; the chain links come from the built log
+    if (int rc = am_plog_size(v->plog, &src.log_base, nullptr, nullptr)) return done(rc);
+    if (int rc = am_plog_append_built(v->plog, &dc, o.src, o.key_off, m, maxk)) return done(rc);
+  }
   src.d_keys = o.keys;
   std::vector<uint64_t> keys(m);
   src.koff.resize(m + 1), src.ktype.resize(m), src.src.resize(n), src.bvoff.resize(n + 1);
@@ -874,6 +922,7 @@ int am_vnode_relabel(am_vnode *v, const uint64_t *old_labels, const uint64_t *ne
   AM_LOCK(v->ctx);
   int rc = am_store_relabel(v->ctx, v->st, old_labels, new_labels, n);
   if (!rc) rc = am_snapcache_relabel(v->ctx, v->sc, v->st->dev.key_type, old_labels, new_labels, n);
+  if (!rc && v->plog) rc = am_plog_relabel(v->plog, old_labels, new_labels, n);
   return rc;
 }
 

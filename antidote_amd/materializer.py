@@ -8,6 +8,8 @@
         -> Store.update(new_log, prune)
     materializer_vnode:load_from_log_to_tables/2 + load_ops/2 (:288-319)
         -> Materializer.load_ops(n_dc, ops_by_key, key_types) (a Vnode)
+    materializer_vnode:get_from_snapshot_log/3 -> logging_vnode:get_up_to_time/5
+        -> PartitionLog.read(reads, horizon); Materializer.vnode(n_dc, n_keys, logged=True)
     stable_time_functions:get_min_time/1 + meta_data_sender:update_stable/3
         -> antidote_amd.gst
 
@@ -351,18 +353,90 @@ class SnapshotCache:
             self.handle = ctypes.c_void_p()
 
 
+class PartitionLog:
+    """The partition's log in HBM (am_plog): the committed transactions in commit order, and the
+    cold read logging_vnode:get_up_to_time/5 + materialize/4 serve from it
+    (src/logging_vnode.erl:522-545, 676-779; src/materializer_vnode.erl:415-419)."""
+
+    def __init__(self, mat: "Materializer", n_dc: int, cap_tx: int = 1024, cap_eff: int = 4096, cap_var: int = 4096,
+                 borrowed: Optional[ctypes.c_void_p] = None):
+        self.mat, self.n_dc, self.owned = mat, n_dc, borrowed is None
+        self.handle = ctypes.c_void_p() if borrowed is None else borrowed  # borrowed: a logged Vnode's log
+        if borrowed is None:
+            abi.check(mat.L.am_plog_create(mat.ctx, n_dc, cap_tx, cap_eff, cap_var, ctypes.byref(self.handle)),
+                      "am_plog_create")
+
+    def append(self, transactions):
+        """A batch of committed transactions behind the log (am_plog_append_host): a Commits, or
+        what Commits takes.  An invalid batch raises and leaves the log as it was."""
+        cm = transactions if isinstance(transactions, Commits) else Commits(self.n_dc, transactions)
+        s = cm.as_struct()
+        abi.check(self.mat.L.am_plog_append_host(self.handle, ctypes.byref(s)), "am_plog_append_host")
+
+    def size(self) -> Tuple[int, int, int]:
+        """(transactions, effects, variable words) in the log."""
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        abi.check(self.mat.L.am_plog_size(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "am_plog_size")
+        return int(a.value), int(b.value), int(c.value)
+
+    def key_ops(self, key: int, horizon: Optional[int] = None) -> List[int]:
+        """The global effect indices of the key's chain among the first `horizon` transactions
+        (None: the whole log), oldest first, whatever their clocks (am_plog_key_ops)."""
+        import numpy as np
+        n_tx, n_eff, _ = self.size()
+        out = np.zeros(max(n_eff, 1), np.uint64)
+        n = ctypes.c_uint64()
+        abi.check(self.mat.L.am_plog_key_ops(self.handle, key, n_tx if horizon is None else horizon, n_eff,
+                                             out.ctypes.data, ctypes.byref(n)), "am_plog_key_ops")
+        return [int(x) for x in out[:int(n.value)]]
+
+    def read(self, reads: Sequence[Read], horizon: Optional[Sequence[int]] = None, set_capacity=None) -> HostBatch:
+        """Every read served from the log (am_plog_read_host; read.base_* are ignored): the key's
+        logged effects among the first horizon[i] transactions (None: the whole log) whose
+        transaction's snapshot_time is vectorclock:le the read clock, ids 0, 1, ... oldest first,
+        materialized from new() under the clock {}."""
+        import numpy as np
+        hb = HostBatch(self.n_dc, reads, set_capacity)
+        b, r = hb.structs()
+        hz = np.ascontiguousarray(horizon, np.uint64) if horizon is not None else None
+        abi.check(self.mat.L.am_plog_read_host(self.mat.ctx, self.handle, ctypes.byref(b),
+                                               hz.ctypes.data if hz is not None else None, ctypes.byref(r)),
+                  "am_plog_read_host")
+        return hb
+
+    def close(self):
+        if self.handle:
+            if self.owned and self.mat.ctx:
+                self.mat.L.am_plog_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+
 class Vnode:
     """One partition's materializer_vnode state on the device (am_vnode): the ops cache and the
     snapshot cache, driven by op_insert_gc/3 and internal_read/7 with the reference's GC
-    (src/materializer_vnode.erl:371-376, 515-563, 622-647)."""
+    (src/materializer_vnode.erl:371-376, 515-563, 622-647).  logged: the vnode keeps the
+    partition's log (am_vnode_create_logged): commits are appended to it, and a read no cached
+    snapshot serves is read from it (get_from_snapshot_log) instead of ending as AM_ERR_COLD_PATH."""
 
-    def __init__(self, mat: "Materializer", n_dc: int, n_keys: int):
-        self.mat, self.n_dc, self.n_keys = mat, n_dc, n_keys
+    def __init__(self, mat: "Materializer", n_dc: int, n_keys: int, logged: bool = False):
+        self.mat, self.n_dc, self.n_keys, self.logged = mat, n_dc, n_keys, logged
         self.handle = ctypes.c_void_p()
-        abi.check(mat.L.am_vnode_create(mat.ctx, n_dc, n_keys, ctypes.byref(self.handle)), "am_vnode_create")
+        if logged:
+            abi.check(mat.L.am_vnode_create_logged(mat.ctx, n_dc, n_keys, ctypes.byref(self.handle)),
+                      "am_vnode_create_logged")
+        else:
+            abi.check(mat.L.am_vnode_create(mat.ctx, n_dc, n_keys, ctypes.byref(self.handle)), "am_vnode_create")
+
+    @property
+    def log(self) -> Optional[PartitionLog]:
+        """The vnode's partition log (borrowed: valid while the vnode is), or None for a plain vnode."""
+        h = ctypes.c_void_p()
+        abi.check(self.mat.L.am_vnode_log(self.handle, ctypes.byref(h)), "am_vnode_log")
+        return PartitionLog(self.mat, self.n_dc, borrowed=h) if h else None
 
     def insert(self, ops_by_key: Sequence[Sequence[Op]], key_types: Sequence[int]):
-        """op_insert_gc/3 for every op (each key's ops oldest -> newest; op ids are assigned)."""
+        """op_insert_gc/3 for every op (each key's ops oldest -> newest; op ids are assigned).  A
+        logged vnode raises (AM_ERR_UNSUPPORTED): a per-key log has no commit order."""
         log = HostLog(self.n_dc, ops_by_key, key_types=key_types)
         s = log.as_struct()
         abi.check(self.mat.L.am_vnode_insert_host(self.handle, ctypes.byref(s)), "am_vnode_insert_host")
@@ -380,7 +454,9 @@ class Vnode:
             self.n_keys = max(self.n_keys, int(cm.key[:cm.n_eff].max()) + 1)  # keys past the key space grow it
 
     def read(self, reads: Sequence[Read], should_gc: Optional[Sequence[bool]] = None, set_capacity=None) -> HostBatch:
-        """internal_read/7 per read (read.base_* ignored); ('error', AM_ERR_COLD_PATH) for the log path."""
+        """internal_read/7 per read (read.base_* ignored).  A read with no cached snapshot at or
+        below its clock takes the log path: a logged vnode serves it from its log; on a plain vnode
+        (logged=False) the status ('error', AM_ERR_COLD_PATH) remains and the caller reads the log."""
         import numpy as np
         hb = HostBatch(self.n_dc, reads, set_capacity)
         b, r = hb.structs()
@@ -510,8 +586,11 @@ class Materializer:
     def snapshot_cache(self, store: Store, n_keys: int) -> "SnapshotCache":
         return SnapshotCache(self, store, n_keys)
 
-    def vnode(self, n_dc: int, n_keys: int) -> Vnode:
-        return Vnode(self, n_dc, n_keys)
+    def vnode(self, n_dc: int, n_keys: int, logged: bool = False) -> Vnode:
+        return Vnode(self, n_dc, n_keys, logged)
+
+    def partition_log(self, n_dc: int, cap_tx: int = 1024, cap_eff: int = 4096, cap_var: int = 4096) -> PartitionLog:
+        return PartitionLog(self, n_dc, cap_tx, cap_eff, cap_var)
 
     def materialize(self, type_: int, txid: Optional[int], min_snapshot_time: Dict[int, int],
                     ops_newest_first: Sequence[Tuple[int, Op]], base_clock: Optional[Dict[int, int]] = None,

@@ -57,9 +57,11 @@ class PartitionedReader:
     """One node's partitions on one GPU: a vnode over the concatenated key spaces."""
 
     def __init__(self, mat: Materializer, n_partitions: int, n_dc: int,
-                 objects: Dict[int, Tuple[int, Sequence[Op]]]):
+                 objects: Dict[int, Tuple[int, Sequence[Op]]], logged: bool = False):
         """objects: Key -> (Type, committed ops oldest -> newest), inserted through
-        op_insert_gc/3 (am_vnode_insert_host: ids, write-triggered GC)."""
+        op_insert_gc/3 (am_vnode_insert_host: ids, write-triggered GC).  logged: the vnode keeps
+        the partitions' log, so no read ends as AM_ERR_COLD_PATH; its objects start without ops and
+        take them through commit() (a per-key op list has no commit order)."""
         self.mat, self.n_partitions, self.n_dc = mat, n_partitions, n_dc
         L = abi.lib()
         per_part: List[List[int]] = [[] for _ in range(n_partitions)]
@@ -76,9 +78,19 @@ class PartitionedReader:
         self.part_key_base = np.array(base, np.uint64)
         # submitted reads not yet waited on: close() waits for them; a dropped one waits in __del__
         self._pending = weakref.WeakSet()
-        self.vnode: Vnode = mat.vnode(n_dc, max(len(order), 1))
-        if order:
+        if logged and any(len(objects[k][1]) for k in order):
+            raise ValueError("a logged reader's objects start without ops: commit() them")
+        self.vnode: Vnode = mat.vnode(n_dc, max(len(order), 1), logged)
+        if order and not logged:
             self.vnode.insert([list(objects[k][1]) for k in order], [objects[k][0] for k in order])
+
+    def commit(self, transactions):
+        """clocksi_vnode:commit/5 for a batch of committed transactions over the node's keys (as
+        Vnode.commit takes them, [(dc, commit_time, snap, txid, [(Key, Type, effect), ...])])."""
+        def vkey(key):
+            p, local = self.where[key]
+            return int(self.part_key_base[p]) + local
+        self.vnode.commit([(d, ct, sn, tx, [(vkey(k), t, e) for k, t, e in effs]) for d, ct, sn, tx, effs in transactions])
 
     def partition_of(self, key: int) -> int:
         return abi.lib().am_key_partition(key, self.n_partitions)
@@ -122,7 +134,8 @@ class PartitionedReader:
     def read_objects(self, objects: Sequence[Tuple[int, int]], snapshot_time: Dict[int, int],
                      txid: Optional[int] = None, write_set: Optional[Dict[int, Sequence]] = None) -> list:
         """Per object ('ok', Value, NewLastOp, LastOpCt, IsNewSS, Count, flags) or
-        ('error', status) -- AM_ERR_COLD_PATH when the read needs the log -- in request order."""
+        ('error', status) -- AM_ERR_COLD_PATH when the read needs the log and the reader keeps none
+        (logged=False) -- in request order."""
         return self.submit(objects, snapshot_time, txid, write_set=write_set).result()
 
     def update_objects(self, objects_updates: Sequence[tuple], snapshot_time: Dict[int, int],

@@ -40,6 +40,10 @@
  *   am_vnode_commit_host    clocksi_vnode:commit/5 -> update_materializer/3 (src/clocksi_vnode.erl:
  *   am_commit_build         499-531, 634-657): a batch of committed transactions' effects, the op log
  *                           over the touched keys built on the device
+ *   am_plog_read            materializer_vnode:get_from_snapshot_log/3 -> logging_vnode:
+ *   am_vnode_create_logged  get_up_to_time/5 (src/materializer_vnode.erl:415-419, src/logging_vnode.erl:
+ *                           522-545, 676-779): the partition's log in HBM, the read no cached
+ *                           snapshot serves rebuilt from it
  *   am_read_objects_submit  clocksi_interactive_coord's read_objects fan-out over a GPU's
  *                           partitions (src/clocksi_interactive_coord.erl:732-747,
  *                           src/clocksi_readitem_server.erl:217-228) as one async batch
@@ -104,7 +108,8 @@ enum am_status {
   AM_ERR_OVERFLOW = 3,              /* result outside int64 (Erlang would bignum)   */
   AM_ERR_CAPACITY = 4,              /* set result larger than the caller's capacity */
   AM_ERR_COLD_PATH = 5,             /* no cached snapshot at or below the read clock:
-                                       get_from_snapshot_log (the log, not the cache) */
+                                       get_from_snapshot_log (the log, not the cache); a vnode
+                                       with a log (am_vnode_create_logged) serves the read */
   AM_ERR_NO_PERMISSIONS = 6,        /* {error, no_permissions} (am_generate_downstream)     */
   AM_ERR_INVALID = -1,
   AM_ERR_HIP = -2,
@@ -820,6 +825,74 @@ int am_commit_build(am_ctx *ctx, uint32_t n_dc, const am_commits *dev_commits, u
  * am_commit_build runs, and only the touched keys, their counts and src come back to plan the GC
  * rounds.  An invalid batch returns AM_ERR_INVALID and leaves the vnode as it was.  Blocks. */
 int am_vnode_commit_host(am_vnode *v, const am_commits *host_commits);
+
+/* ---- the partition log in HBM and the cold read (am_plog.hip) ----
+ * materializer_vnode:get_from_snapshot_log/3 -> logging_vnode:get_up_to_time/5
+ * (src/materializer_vnode.erl:415-419, src/logging_vnode.erl:522-545, 586-591, 676-779): a read with
+ * no cached snapshot at or below its clock (AM_ERR_COLD_PATH above) is answered from the partition's
+ * log.  The log here is the sequence of commit batches (am_commits) as am_vnode_commit_host takes
+ * them -- the committed content of disk_log, in the order the commit records were appended; durability
+ * stays with the caller.  Append-only and transaction-major: per transaction dc, commit_time, one
+ * snap_vc row, snap_pres (every DC when the batch has none) and txid (0 when the batch has none); per
+ * effect key, type, eff_meta, p0, p1, its variable words, and a 16-byte link {the previous effect on
+ * the same key, the effect's transaction}, so a key's effects are a chain from its newest one.
+ * Capacities double (small ones are legal); an append costs O(batch) on host and device. */
+typedef struct am_plog am_plog;
+int am_plog_create(am_ctx *ctx, uint32_t n_dc, uint64_t cap_tx, uint64_t cap_eff, uint64_t cap_var, am_plog **out);
+int am_plog_destroy(am_plog *plog);
+/* A host batch behind the log; transactions without effects count (a horizon is a number of
+ * transactions).  Validated as am_commit_build validates: an invalid batch returns AM_ERR_INVALID and
+ * leaves the log as it was.  Blocks. */
+int am_plog_append_host(am_plog *plog, const am_commits *host_commits);
+/* transactions, effects and variable words in the log (NULL outputs are skipped) */
+int am_plog_size(const am_plog *plog, uint64_t *n_tx, uint64_t *n_eff, uint64_t *n_var);
+/* Test accessor: the global effect indices of key's chain among the first `horizon` transactions,
+ * oldest first, not filtered by any clock, to the host array eff_idx [cap]; *n = their number
+ * (AM_ERR_CAPACITY when cap is smaller: nothing is written). */
+int am_plog_key_ops(am_plog *plog, uint64_t key, uint64_t horizon, uint64_t cap, uint64_t *eff_idx, uint64_t *n);
+/* Every read of the batch served from the log, whatever a snapshot cache holds (the batch's base
+ * members are ignored): for read r, among the first horizon[r] transactions (dev_horizon [n], or NULL
+ * = the whole log; when op_insert_gc/3 of transaction i's ops runs its GC read the log holds
+ * transactions 0..i, so that read's horizon is i + 1), every effect on the read's key, in log order,
+ * whose transaction's snapshot_time is vectorclock:le the read clock (over the keys of both, a missing
+ * entry 0; the snapshot_time itself, not the commit-substituted vector) is an op; the survivors get
+ * ids 0, 1, 2, ... oldest first and are materialized (materialize/4) from new(Type) with
+ * last_op_id 0 under the snapshot clock {} -- a clock, not ignore, so LastOpCt is never ignore.
+ * Outputs are am_materialize's: a type mismatch among the survivors is AM_ERR_CORRUPTED_OPS_CACHE, an
+ * included bad effect AM_ERR_UNEXPECTED_OPERATION, a survivor outside the read clock lowers
+ * NewLastOp to its id - 1 (-1 for id 0); effects that fail the filter are absent altogether.  A read
+ * without survivors gives AM_OK, new(), NewLastOp 0, LastOpCt {}, IsNewSS 0, Count 0.
+ * Three kernels and two scans build a plain am_op_log over "keys" = the reads (one readback of its
+ * sizes), which am_materialize's tiers read as it is: O(the read keys' logged effects) on the
+ * device, O(reads) on the host, whatever the log's length.  Device pointers. */
+int am_plog_read(am_ctx *ctx, am_plog *plog, const am_read_batch *dev_batch, const uint64_t *dev_horizon,
+                 am_read_result *dev_res);
+/* The same with host batch, horizons and result; blocks. */
+int am_plog_read_host(am_ctx *ctx, am_plog *plog, const am_read_batch *host_batch, const uint64_t *host_horizon,
+                      am_read_result *host_res);
+/* A vnode that keeps its partition's log: it answers every internal_read/7 the reference answers.
+ * am_vnode_create's vnode behaves exactly as before, AM_ERR_COLD_PATH included.  On a logged vnode
+ *   am_vnode_commit_host   appends the batch to the log first (append_commit before
+ *                          update_materializer, src/clocksi_vnode.erl:517-519; the remote path
+ *                          likewise, src/inter_dc_dep_vnode.erl:146-152), the chain links from the
+ *                          am_commit_build output it makes anyway; each GC read of op_insert_gc/3
+ *                          carries the horizon of its trigger op's transaction, so a GC read that
+ *                          goes cold sees the log as the reference's does.  An invalid batch leaves
+ *                          the log and the vnode unchanged.
+ *   am_vnode_read_host, am_read_objects_*, am_read_objects_ws_*, am_update_objects_*
+ *                          a read with no cached snapshot at or below its clock is read from the
+ *                          whole log (am_plog_read's rules) before the write set and the updates
+ *                          see its row, and its snapshot is stored as materialize_snapshot/7
+ *                          stores a response that is not the newest snapshot: iff ShouldGC, through
+ *                          internal_store_ss/4 -> insert_bigger -> snapshot_insert_gc/4 as for any
+ *                          read (last_op_id in log ids, as the reference does).  A round with a log
+ *                          pays one small readback to learn whether any read went cold.
+ *   am_vnode_insert_host   AM_ERR_UNSUPPORTED, the vnode as it was: a per-key host log has no commit
+ *                          order.
+ *   am_vnode_relabel       also maps the log's label words, by each effect's type.
+ * am_vnode_log: the vnode's log (borrowed; NULL for a plain vnode). */
+int am_vnode_create_logged(am_ctx *ctx, uint32_t n_dc, uint64_t n_keys, am_vnode **out);
+int am_vnode_log(am_vnode *v, am_plog **plog);
 
 /* ---- op-cache ingestion + garbage collection ----
  * Builds a new store from `st` (st is unchanged; destroy it when no read uses it):
