@@ -37,6 +37,7 @@
 // word per born group (birth op | kill op) instead of one record per birth and kill slot.
 #pragma once
 #include "am_block.h"
+#include "am_inclwin.h"
 
 namespace amk_grp {
 using namespace amk;
@@ -1270,14 +1271,37 @@ __device__ __forceinline__ uint32_t incl_tile(const Ent &x, const PkRead<DMAX> &
   return ib;
 }
 
+// the same test for the ops of the lane that the commit word left undecided (bits of win, the
+// window of am_inclwin.h): ops outside win neither pass here nor touch the maxima
+template <int DMAX, int OPL, class Ent>
+__device__ __forceinline__ uint32_t incl_tile_w(const Ent &x, const PkRead<DMAX> &pk, uint32_t win,
+                                                uint32_t (&mx)[DMAX]) {
+  uint32_t ib = 0;
+#pragma unroll
+  for (int k = 0; k < OPL; ++k) {
+    bool in = (win >> k) & 1u;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) in = in && x(k, d) <= pk.thr[d];
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) mx[d] = max(mx[d], in ? x(k, d) : 0u);
+    ib |= (uint32_t)in << k;
+  }
+  return ib;
+}
+
 // LAG: the read streams the lag view (am_op_log.lag_ct / lag / key_lag, 4 + 2 D bytes per op)
 // and rebuilds each packed entry X[d] - K = lag_ct - key_lag[d] - lag[d] in u32 (exact: the entry
 // fits u32 for every op the view holds); else the packed view (4 D bytes per op)
 #ifndef AM_INCL_WAVES
 #define AM_INCL_WAVES 3  // waves per SIMD: the pipelined tile loop holds two tiles (168 VGPRs)
 #endif
+// LAG: the tile loop holds ~100 VGPRs at D = 8 and the escape pass after it 137, two more than
+// four waves leave without spilling; narrower clocks fit four
+#ifndef AM_INCL_LAG_WAVES
+#define AM_INCL_LAG_WAVES(D) ((D) < 8 ? 4 : 3)
+#endif
 template <int DMAX, int TYPE, bool EXACT, bool LAG>
-__global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
+__global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL_WAVES) k_grp_incl(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
                                                        am_retry next, am_retry routed, uint32_t short_opl,
                                                        uint32_t *ibm) {
   const am_op_log L = LA.log();
@@ -1377,40 +1401,97 @@ __global__ void __launch_bounds__(BLOCK, AM_INCL_WAVES) k_grp_incl(am_log_arg LA
       };
       if constexpr (LAG) {
         static_assert(OPL == 4, "four u16 lags per 8-byte load");
-        // software-pipelined: tile t + 1's loads are issued before tile t is evaluated, into the
-        // other of two register sets (no copies between them: a copy would wait for the loads)
+        // The commit word alone decides most ops (am_inclwin.h): only ops in the window
+        // in_lim <= c < out_lim load their lags.  Tiles are walked newest first, so the newest
+        // included ops raise cmax (and with it in_lim) before the older ones are met; the commit
+        // words of tile t - 1 are in flight while tile t is evaluated (two register sets, no
+        // copies between them).  A whole tile the limits decide takes a short path (tile_const).
+        int64_t cinf = AM_IW_NOBOUND;
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d)
+          if (d < (int)nd) cinf = am_iw_fold(cinf, pk.thr[d], lb[d]);
+        am_inclwin iw;
+        am_iw_init(&iw, cinf, pk.never);
+        const uint32_t cin_lim = am_iw_lim(iw.cin), out_lim = am_iw_lim(iw.hi);
+        uint32_t in_lim = am_iw_in_lim(&iw);
         uint32_t cA[OPL], cB[OPL];
-        uint32_t lA[DMAX][2], lB[DMAX][2];
-        auto load = [&](uint64_t t, uint32_t (&c)[OPL], uint32_t (&lw)[DMAX][2]) {
+        auto load = [&](uint64_t t, uint32_t (&c)[OPL]) {
           const uint64_t g = t + (uint64_t)lane * OPL;
 #pragma unroll
           for (int k = 0; k < OPL; ++k) c[k] = 0;
           if (g < off1) ld_n32<OPL>(L.lag_ct + g, c);
-#pragma unroll
-          for (int d = 0; d < DMAX; ++d) {
-            uint2 v = {0, 0};
-            if (d < (int)nd && g < off1) v = *(const uint2 *)(L.lag + (uint64_t)d * stride + g);
-            lw[d][0] = v.x, lw[d][1] = v.y;
-          }
         };
-        auto eval = [&](uint64_t t, const uint32_t (&c)[OPL], const uint32_t (&lw)[DMAX][2]) {
+        // a whole tile of included ops below every maximum, or of excluded ops: no shuffles
+        auto tile_const = [&](uint64_t g, bool in) {
+          if (in) cnt += OPL;
+          else minex = min(minex, (uint32_t)(g - t0));
+          anyc |= (1u << OPL) - 1u;
+          if (lane % LPW == 0) ibm[g >> 5] = in ? ~0u : 0u;  // every word lies inside the read
+        };
+        auto eval = [&](uint64_t t, const uint32_t (&c)[OPL]) {
           const uint64_t g = t + (uint64_t)lane * OPL;
-          uint32_t esc = 0, cand = 0;
           const bool whole = t >= off0 && t + TILE <= off1;
-          // (pad DCs d >= nd: c - lb[d] with lb = 0 lies under the always-passing pad threshold)
-          const auto x = lag_ent(c, lw, lb);
-          const uint32_t ib = whole ? incl_tile<DMAX, OPL, false>(x, pk, g, off0, off1, mx, esc, cand)
-                                    : incl_tile<DMAX, OPL, true>(x, pk, g, off0, off1, mx, esc, cand);
+          if (whole) {
+            static_assert(OPL == 4, "min / max of four words");
+            const uint32_t ch = max(max(c[0], c[1]), max(c[2], c[3]));  // (AM_PK_ESC is the largest word)
+            if (!__ballot(ch >= in_lim)) return tile_const(g, true);
+            const uint32_t cl = min(min(c[0], c[1]), min(c[2], c[3]));
+            if (!__ballot(cl < out_lim || ch == AM_PK_ESC)) return tile_const(g, false);
+          }
+          uint32_t esc = 0, cand = 0, sure = 0;  // sure: 1 + the lane's largest c <= cin
+#pragma unroll
+          for (int k = 0; k < OPL; ++k) {
+            const bool e = c[k] == AM_PK_ESC;
+            const bool inr = whole || (g + k >= off0 && g + k < off1);
+            esc |= (uint32_t)(inr && e) << k;
+            cand |= (uint32_t)(inr && !e) << k;
+            if (inr && c[k] < cin_lim) sure = max(sure, c[k] + 1u);
+          }
+          // the bound without loads, before this tile's own ops are classified
+          if (in_lim < cin_lim) {
+            const uint32_t m = uniform_u32(wave_max_u32_v(sure));
+            if (m) am_iw_raise(&iw, am_iw_cmax_sure(m - 1u)), in_lim = am_iw_in_lim(&iw);
+          }
+          uint32_t ib = 0, win = 0;
+#pragma unroll
+          for (int k = 0; k < OPL; ++k) {
+            const int cl = am_iw_class32(c[k], in_lim, out_lim);
+            ib |= (uint32_t)(cl == AM_IW_IN) << k;
+            win |= (uint32_t)(cl == AM_IW_WINDOW) << k;
+          }
+          ib &= cand, win &= cand;
+          if (__ballot(win != 0)) {  // lanes with an op in the window: a predicated 8-byte load per DC
+            uint32_t lw[DMAX][2];
+#pragma unroll
+            for (int d = 0; d < DMAX; ++d) {
+              uint2 v = {0, 0};
+              if (d < (int)nd && win) v = *(const uint2 *)(L.lag + (uint64_t)d * stride + g);
+              lw[d][0] = v.x, lw[d][1] = v.y;
+            }
+            // (pad DCs d >= nd: c - lb[d] with lb = 0 lies under the always-passing pad threshold)
+            const uint32_t iwb = incl_tile_w<DMAX, OPL>(lag_ent(c, lw, lb), pk, win, mx);
+            ib |= iwb;
+            if (__ballot(iwb != 0)) {  // any lane's maxima bound every lane's
+              int64_t v = AM_IW_NOBOUND;
+#pragma unroll
+              for (int d = 0; d < DMAX; ++d)
+                if (d < (int)nd) v = am_iw_fold(v, mx[d], lb[d]);
+              constexpr int64_t BIAS = 1ll << 32;  // v >= INT32_MIN: unsigned order
+              am_iw_raise(&iw, (int64_t)uniform_u64(wave_max_u64_v((uint64_t)(v + BIAS))) - BIAS);
+              in_lim = am_iw_in_lim(&iw);
+            }
+          }
           tile_out(t, g, ib, esc, cand);
         };
-        load(t0, cA, lA);
-        for (uint64_t t = t0; t < off1; t += 2 * TILE) {
-          const uint64_t t1 = t + TILE;
-          if (t1 < off1) load(t1, cB, lB);
-          eval(t, cA, lA);
-          if (t1 >= off1) break;
-          if (t1 + TILE < off1) load(t1 + TILE, cA, lA);
-          eval(t1, cB, lB);
+        const uint64_t tl = t0 + (off1 - 1 - t0) / TILE * TILE;  // the last tile
+        load(tl, cA);
+        for (uint64_t t = tl;; t -= 2 * TILE) {
+          if (t > t0) load(t - TILE, cB);
+          eval(t, cA);
+          if (t == t0) break;
+          if (t - TILE > t0) load(t - 2 * TILE, cA);
+          eval(t - TILE, cB);
+          if (t - TILE == t0) break;
         }
       } else {
         for (uint64_t t = t0; t < off1; t += TILE) {

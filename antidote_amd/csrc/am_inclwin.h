@@ -1,0 +1,83 @@
+// am_inclwin.h -- the commit-word window of a snapshot read over the lag view (host and device;
+// plain C, no HIP: tests/test_inclwindow.py builds it with a host compiler).
+//
+// An op the lag view holds (c = lag_ct[p] != AM_PK_ESC) has, per DC d < nd, the entry
+//   x_d = c - lb_d - lag_d,   lb_d = key_lag[k][d] (int32),   lag_d in [0, 0xFFFF],
+// and is included iff x_d <= thr_d for every d (PkRead::thr).  Since the lags are bounded, the
+// 4-byte commit word decides most ops without them.  Per read, in int64:
+//   cin  = min_d (thr_d + lb_d)   c <= cin: every x_d <= c - lb_d <= thr_d        -> included
+//   hi   = cin + 0xFFFF           c >  hi : the DC attaining cin has x_d > thr_d  -> excluded
+//   cmax = min_d (M_d + lb_d)     c <= cmax: every x_d <= M_d, so the op raises no LastOpCt
+//                                 maximum that already stands at M_d or above
+// M_d is any lower bound of the read's final maximum of DC d: the running maximum over included
+// ops (0 before the first: entries are >= 0), or c' - lb_d - 0xFFFF of an op c' <= cin, which
+// gives cmax >= c' - 0xFFFF without a lag load.  Only ops with min(cin, cmax) < c <= hi (the
+// window) need their lags.  Exact in any visiting order; a stale, smaller cmax is always safe.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define AM_IW_HD __host__ __device__ __forceinline__
+#else
+#define AM_IW_HD static inline
+#endif
+
+#define AM_IW_LAG_MAX 0xFFFFll
+#define AM_IW_ESC 0xFFFFFFFFu /* AM_PK_ESC: the lag view does not hold the op */
+
+enum { AM_IW_ESCAPED = 0, AM_IW_OUT = 1, AM_IW_IN = 2, AM_IW_WINDOW = 3 };
+
+typedef struct am_inclwin {
+  int64_t cin;  /* c <= cin: included; negative: nothing is sure-in */
+  int64_t hi;   /* c >  hi : excluded */
+  int64_t cmax; /* c <= min(cin, cmax): included and below every maximum; -1: no bound yet */
+} am_inclwin;
+
+/* one DC's term of a minimum min_d (v_d + lb_d): v the threshold or the maximum, lb the key's
+ * lag base (the int32 as stored, in u32).  Start from AM_IW_NOBOUND; DCs d >= nd take no part. */
+#define AM_IW_NOBOUND INT64_MAX
+AM_IW_HD int64_t am_iw_fold(int64_t acc, uint32_t v, uint32_t lb) {
+  const int64_t t = (int64_t)v + (int64_t)(int32_t)lb;
+  return t < acc ? t : acc;
+}
+/* cin_fold: am_iw_fold over the thresholds of the DCs d < nd.  never (PkRead::never): no op
+ * passes and nothing needs lags. */
+AM_IW_HD void am_iw_init(am_inclwin *w, int64_t cin_fold, int never) {
+  const int64_t cin = (never || cin_fold == AM_IW_NOBOUND) ? -1 - AM_IW_LAG_MAX : cin_fold;
+  w->cin = cin, w->hi = cin + AM_IW_LAG_MAX, w->cmax = -1;
+}
+AM_IW_HD void am_iw_setup(am_inclwin *w, const uint32_t *thr, const uint32_t *lb, uint32_t nd, int never) {
+  int64_t f = AM_IW_NOBOUND;
+  for (uint32_t d = 0; d < nd; ++d) f = am_iw_fold(f, thr[d], lb[d]);
+  am_iw_init(w, f, never);
+}
+
+/* the bound a set of running maxima m[] (over included ops; 0 where none yet) gives */
+AM_IW_HD int64_t am_iw_cmax_of(const uint32_t *m, const uint32_t *lb, uint32_t nd) {
+  int64_t f = AM_IW_NOBOUND;
+  for (uint32_t d = 0; d < nd; ++d) f = am_iw_fold(f, m[d], lb[d]);
+  return nd ? f : -1;
+}
+/* the bound an op with c <= cin gives without its lags */
+AM_IW_HD int64_t am_iw_cmax_sure(uint32_t c) { return (int64_t)c - AM_IW_LAG_MAX; }
+AM_IW_HD void am_iw_raise(am_inclwin *w, int64_t cmax) { w->cmax = cmax > w->cmax ? cmax : w->cmax; }
+
+AM_IW_HD int am_iw_sure_in(const am_inclwin *w, uint32_t c) { return c != AM_IW_ESC && (int64_t)c <= w->cin; }
+/* escape first: AM_PK_ESC lies above every hi */
+AM_IW_HD int am_iw_class(const am_inclwin *w, uint32_t c) {
+  if (c == AM_IW_ESC) return AM_IW_ESCAPED;
+  if ((int64_t)c > w->hi) return AM_IW_OUT;
+  if ((int64_t)c <= (w->cin < w->cmax ? w->cin : w->cmax)) return AM_IW_IN;
+  return AM_IW_WINDOW;
+}
+
+/* The same classes from exclusive u32 limits, one compare each: for a commit word c <= 2^32 - 2,
+ * c < am_iw_lim(v) iff c <= v.  in_lim = am_iw_lim(min(cin, cmax)), out_lim = am_iw_lim(hi);
+ * AM_PK_ESC lies at or above every limit, so escape is still tested first. */
+AM_IW_HD uint32_t am_iw_lim(int64_t v) { return v < 0 ? 0u : v >= 0xFFFFFFFEll ? 0xFFFFFFFFu : (uint32_t)v + 1u; }
+AM_IW_HD uint32_t am_iw_in_lim(const am_inclwin *w) { return am_iw_lim(w->cin < w->cmax ? w->cin : w->cmax); }
+AM_IW_HD int am_iw_class32(uint32_t c, uint32_t in_lim, uint32_t out_lim) {
+  if (c == AM_IW_ESC) return AM_IW_ESCAPED;
+  if (c >= out_lim) return AM_IW_OUT;
+  return c < in_lim ? AM_IW_IN : AM_IW_WINDOW;
+}
