@@ -295,21 +295,8 @@ __device__ __forceinline__ void esc_pass(const am_op_log &L, uint32_t nd, const 
   }
 }
 
-// the same for a fresh read whose bits live in the global bitmap gbm (bit = op slot); escv: the
-// view the read streamed (pk_vc, or the lag view's lag_ct), whose AM_PK_ESC marks the escapes
-template <int DMAX>
-__device__ void esc_pass_g(const am_op_log &L, uint32_t nd, const ReadU<DMAX> &u, uint64_t off0, uint64_t off1,
-                           uint64_t stride, uint32_t lane, uint32_t *gbm, Acc<DMAX> &a, const uint32_t *escv,
-                           uint64_t K) {
-  for (uint64_t p = off0 + lane; p < off1; p += WAVE) {
-    if (escv[p] != AM_PK_ESC) continue;
-    uint64_t sv[DMAX], ct;
-    uint32_t meta;
-    esc_load<DMAX>(L, nd, stride, p, K, sv, ct, meta);
-    if (eval_op<DMAX, false>(u, meta, ct, sv, u.allmask, false, p, a) && !(meta & AM_META_BAD))
-      atomicOr(&gbm[p >> 5], 1u << (p & 31));
-  }
-}
+// (a fresh read whose bits live in the global bitmap walks its escapes the same way, in
+// k_grp_incl's deferred phase)
 
 // a wave's scalar outputs (in every lane): packed partials (u32, relative to K) and, when
 // `full` (wave-uniform: the full view, or escaped ops), full-width partials.  mxl: lane d's
@@ -1220,7 +1207,12 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
 // Count, status}; k_grp_wave<BM> then streams the records against those bits and gathers the
 // survivors.  A wave takes 32 CONSECUTIVE reads at a time and their scalar outputs leave through
 // LDS as one coalesced store per column (single-lane stores of reads far apart write partial
-// lines of the output columns, each line written back once per writer).
+// lines of the output columns, each line written back once per writer).  Ops outside the
+// streamed view (escaped ops, rare) are evaluated once per batch, after its reads' tile loops:
+// a read that met any leaves its lanes' escape marks in a scratch row (escr: 512 bytes per read
+// slot of the wave, written for such reads only) and its in-view partials in the LDS rows, and
+// the deferred phase ORs the included escaped ops into the bitmap and merges their partials in
+// before the outputs are derived.
 constexpr uint32_t IWB = 32;  // reads per wave batch
 __device__ __forceinline__ uint32_t wave_min_u32_v(uint32_t v) {
 #define S_(C) v = min(v, dpp32<C>(v));
@@ -1237,11 +1229,13 @@ template <int DMAX>
 struct ISmem {
   ISlot slot[IWB];
   uint32_t mx[DMAX][WAVE];      // one read's per-lane LastOpCt maxima, transposed for the reduction
-  uint64_t ct[DMAX][IWB];       // the batch's outputs, by read
-  int64_t nlo[IWB];
+  // the batch's partials, by read: the in-view values as the tile loop leaves them, then merged
+  // with the escaped ops' (the deferred phase); the outputs are derived from them once, as the
+  // batch leaves
+  uint64_t ct[DMAX][IWB];       // LastOpCt maxima, not yet masked by the presence
+  uint64_t mex[IWB];            // the first excluded op's slot (NONE: none)
   uint32_t count[IWB], pres[IWB];
-  int32_t status[IWB];
-  uint32_t flags[IWB];
+  uint32_t flags[IWB];          // with FLAG_BAD
 };
 
 // ops [g, g + OPL) of the lane (OPL consecutive slots, g OPL-aligned), their entries x those of
@@ -1292,18 +1286,25 @@ __device__ __forceinline__ uint32_t incl_tile_w(const Ent &x, const PkRead<DMAX>
 // LAG: the read streams the lag view (am_op_log.lag_ct / lag / key_lag, 4 + 2 D bytes per op)
 // and rebuilds each packed entry X[d] - K = lag_ct - key_lag[d] - lag[d] in u32 (exact: the entry
 // fits u32 for every op the view holds); else the packed view (4 D bytes per op)
+//
+// Waves per SIMD, by clock width D.  The pass is bound by the chain of dependent loads of a read
+// (lag bases and newest commit words, then each window tile's lag lines), which more waves
+// cover.  The per-read loop holds the tile loop and the reduction only: escaped ops are
+// evaluated after the batch's loop, where no tile state is live, and what the batch's set-up
+// and outputs derive from the lane number is computed per batch (sl_, ol), so neither weighs on
+// the tile loop's registers.  LAG (two tiles of commit words, the lag words of one, the window
+// state): 95-96 VGPRs at D = 8, five waves without a vector spill.  Packed (the tile's D x 4
+// entries): 103 VGPRs at D = 8, four waves (fifteen spilled at five).
 #ifndef AM_INCL_WAVES
-#define AM_INCL_WAVES 3  // waves per SIMD: the pipelined tile loop holds two tiles (168 VGPRs)
+#define AM_INCL_WAVES(D) 4
 #endif
-// LAG: the tile loop holds ~100 VGPRs at D = 8 and the escape pass after it 137, two more than
-// four waves leave without spilling; narrower clocks fit four
 #ifndef AM_INCL_LAG_WAVES
-#define AM_INCL_LAG_WAVES(D) ((D) < 8 ? 4 : 3)
+#define AM_INCL_LAG_WAVES(D) 5
 #endif
 template <int DMAX, int TYPE, bool EXACT, bool LAG>
-__global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL_WAVES) k_grp_incl(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
+__global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL_WAVES(DMAX)) k_grp_incl(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
                                                        am_retry next, am_retry routed, uint32_t short_opl,
-                                                       uint32_t *ibm) {
+                                                       uint32_t *ibm, uint64_t *escr) {
   const am_op_log L = LA.log();
   constexpr int OPL = 4;
   constexpr uint64_t TILE = (uint64_t)WAVE * OPL;
@@ -1312,7 +1313,6 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
   ISmem<DMAX> &sm = smem[threadIdx.x >> 6];
   ISlot *sl = sm.slot;
   const uint32_t lane = threadIdx.x & (WAVE - 1);
-  const uint64_t lt = (1ull << lane) - 1ull;
   const uint32_t nd = EXACT ? (uint32_t)DMAX : L.n_dc;
   const uint64_t stride = L.snap_stride ? L.snap_stride : L.n_ops;
   const uint32_t sel0 = S.idx ? uniform_u32(S.range[0]) : 0u;
@@ -1325,22 +1325,28 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
 
   for (uint64_t b0 = gw * IWB; b0 < nsel; b0 += (uint64_t)IWB * W) {
     // ---- lane j < IWB: read b0 + j -> slot j (errors and hand-offs leave here) ----
-    const uint64_t ii = b0 + lane;
+    // (sl_: the lane number, opaque to the compiler -- what the batch's set-up and outputs derive
+    //  from it is computed where it is used, per batch, not once per kernel and then held in
+    //  registers across the tile loop, whose budget has no room for it)
+    uint32_t sl_ = lane, sopl = short_opl;  // (sopl: the same for the mask wave_takes makes of it)
+    asm volatile("" : "+v"(sl_));
+    asm volatile("" : "+s"(sopl));
+    const uint64_t ii = b0 + sl_;
     bool elig = false, hand = false, route = false;
     uint64_t rr = 0;
-    if (lane < IWB && ii < nsel) {
+    if (sl_ < IWB && ii < nsel) {
       GMeta mm;
       read_meta(L, B, S.idx ? (uint64_t)S.idx[sel0 + ii] : ii, TYPE, mm);
       rr = mm.r;
       if (mm.st != AM_OK) {
         R.status[mm.r] = mm.st, R.flags[mm.r] = 0;
-      } else if (!wave_takes(L, B, mm, short_opl)) {
+      } else if (!wave_takes(L, B, mm, sopl)) {
         hand = true;
       } else if (LAG && routed.list && L.key_lag[mm.key * nd] == AM_LAG_ROUTED) {
         route = true;  // a packed-routed key: the packed instantiation's (launch_split)
       } else {
         elig = true;
-        ISlot &w = sl[lane];
+        ISlot &w = sl[sl_];
         w.off0 = mm.off0, w.K = L.key_tbase[mm.key], w.idb = L.key_id_base ? L.key_id_base[mm.key] : 1;
         w.key = mm.key;
         w.r = (uint32_t)mm.r, w.nops = (uint32_t)(mm.off1 - mm.off0);
@@ -1349,12 +1355,14 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
     const uint64_t hm = __ballot(hand);
     if (hm) {
       uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(next.count, (uint32_t)__popcll(hm));
+      if (sl_ == 0) base = atomicAdd(next.count, (uint32_t)__popcll(hm));
       base = uniform_u32(base);
-      if (hand) next.list[base + (uint32_t)__popcll(hm & lt)] = (uint32_t)rr;
+      if (hand) next.list[base + (uint32_t)__popcll(hm & ((1ull << sl_) - 1ull))] = (uint32_t)rr;
     }
-    if (LAG) retry_append(routed, route, (uint32_t)rr, lane);
+    if (LAG) retry_append(routed, route, (uint32_t)rr, sl_);
     const uint64_t emask = __ballot(elig);
+    uint32_t escmask = 0;  // the batch's reads with escaped ops (wave-uniform): the deferred phase's
+    uint64_t *const escw = escr + (gw * IWB) * WAVE;  // this wave's escape-mark rows, one per slot
     wave_sync();
 
     for (uint64_t em = emask; em; em &= em - 1) {
@@ -1527,70 +1535,111 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
           const u32x4 a0 = *(const u32x4 *)&sm.mx[d][8 * c], a1 = *(const u32x4 *)&sm.mx[d][8 * c + 4];
           m = max(max(max(a0.x, a0.y), max(a0.z, a0.w)), max(max(a1.x, a1.y), max(a1.z, a1.w)));
         }
-        m = max(m, (uint32_t)__shfl_xor((int)m, 1));
-        m = max(m, (uint32_t)__shfl_xor((int)m, 2));
-        m = max(m, (uint32_t)__shfl_xor((int)m, 4));
+        // lanes ^ 1, ^ 2, then the other quad of the eight (row_half_mirror): no lane addresses,
+        // which the compiler would compute once per batch and hold across the tile loop
+        m = max(m, dpp32<0xB1>(m));
+        m = max(m, dpp32<0x4E>(m));
+        m = max(m, dpp32<0x141>(m));
       }
-      // lane d: DC d's packed maximum (relative to K)
-      const uint32_t mxd = (uint32_t)__shfl((int)m, (int)((lane & 7u) << 3));
-      uint64_t mxl = (lane < nd && count_p) ? pk.K + mxd : 0;
-      uint32_t count = count_p, flags = cands ? pk.miss : 0u, pres = count_p ? u.allmask : 0u;
-      uint64_t min_excl = minex == 0xFFFFFFFFu ? NONE : t0 + minex;
-      if (escs) {  // rare: ops outside the streamed view, through the escape reader (bits ORed in)
-        Acc<DMAX> a;
-        a.reset();
-        __builtin_amdgcn_s_waitcnt(0);
-        if (__ballot(escm == ~0ull)) {  // a long key's late tiles: the wave walks its escape marks
-          esc_pass_g<DMAX>(L, nd, u, off0, off1, stride, lane, ibm, a, LAG ? L.lag_ct : L.pk_vc, LAG ? pk.K : NONE);
-        } else {  // the lane's own escaped ops, marked by the tile loop: no second walk of the key
-          for (uint64_t m = escm; m; m &= m - 1) {
-            const uint32_t b = (uint32_t)__builtin_ctzll(m);
-            const uint64_t p = t0 + (uint64_t)(b / OPL) * TILE + (uint64_t)lane * OPL + b % OPL;
-            uint64_t sv[DMAX], ct;
-            uint32_t meta;
-            esc_load<DMAX>(L, nd, stride, p, LAG ? pk.K : NONE, sv, ct, meta);
-            if (eval_op<DMAX, false>(u, meta, ct, sv, u.allmask, false, p, a) && !(meta & AM_META_BAD))
-              atomicOr(&ibm[p >> 5], 1u << (p & 31));
-          }
-        }
-        count += wave_sum_u32_v(a.count), flags |= wave_or_u32_v(a.flags), pres |= wave_or_u32_v(a.pres);
-        min_excl = wave_min_u64_v(umin64(min_excl, a.min_excl));
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) {
-          if (d >= (int)nd) continue;
-          const uint64_t am = wave_max_u64_v(a.mx[d]);
-          if ((uint32_t)d == lane) mxl = umax64(mxl, am);
-        }
-      }
-      // the read's outputs into the batch's LDS rows (slot j); they leave with the batch
-      const bool ign = count == 0;  // base ignore
-      const uint32_t opres = ign ? 0u : pres;
-      if (lane < nd) sm.ct[lane][j] = ((opres >> lane) & 1u) ? mxl : 0;
+      // lane d: DC d's packed maximum (relative to K), from lane 8 d (its address from the opaque
+      // lane number, for the same reason)
+      uint32_t ql = lane;
+      asm volatile("" : "+v"(ql));
+      const uint32_t mxd = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((ql & 7u) << 5), (int)m);
+      // the read's in-view partials into the batch's LDS rows (slot j).  Ops outside the streamed
+      // view (rare) are not evaluated here: the read leaves its lanes' escape marks in the wave's
+      // scratch row j and its bit in escmask, and the deferred phase below merges them in
+      if (lane < nd) sm.ct[lane][j] = count_p ? pk.K + mxd : 0;
       if (lane == 0) {
-        sm.status[j] = (flags & FLAG_BAD) ? AM_ERR_UNEXPECTED_OPERATION : AM_OK;
-        sm.flags[j] = flags & 0xFFu;
-        sm.count[j] = count;
-        sm.pres[j] = opres;
-        sm.nlo[j] = new_last_op_b(L, uniform_u64(sl[j].idb), off0, off1, min_excl);
+        sm.flags[j] = cands ? pk.miss : 0u;
+        sm.count[j] = count_p;
+        sm.pres[j] = count_p ? u.allmask : 0u;
+        sm.mex[j] = minex == 0xFFFFFFFFu ? NONE : t0 + minex;
+      }
+      if (escs) {
+        escw[(uint64_t)j * WAVE + lane] = escm;
+        escmask |= 1u << j;
       }
       wave_sync();  // sm.mx is rewritten by the next read
     }
-    // ---- the batch's outputs: one coalesced store per column (lane j: read b0 + j) ----
-    if ((emask >> lane) & 1ull) {
-      const uint64_t r = rr;
-      const int32_t st = sm.status[lane];
+    // ---- the deferred phase: the escaped ops of the batch's reads that met any, through the
+    //      escape reader; the included ones' bits are ORed into the bitmap and their partials
+    //      merged into the read's row.  No tile state is live here, so the D-wide u64 values of
+    //      esc_load / eval_op do not weigh on the tile loop's registers ----
+    if (escmask) __builtin_amdgcn_s_waitcnt(0);  // the batch's bitmap words and mark rows are out
+    for (uint32_t xm = escmask; xm; xm &= xm - 1) {
+      const uint32_t j = (uint32_t)__builtin_ctz(xm);
+      const uint64_t off0 = uniform_u64(sl[j].off0), off1 = off0 + uniform_u32(sl[j].nops);
+      const uint64_t K = uniform_u64(sl[j].K), t0 = off0 & ~31ull;
+      const uint64_t escm = escw[(uint64_t)j * WAVE + lane];
+      Acc<DMAX> a;
+      a.reset();
+      // The lane's own escaped ops, marked by the tile loop: no second walk of the key.  A long
+      // key's late tiles have no mark bits (a lane's ~0): the wave walks the escape marks of the
+      // view it streamed instead, lane l the slots off0 + l, + 64, ...  One evaluation site serves
+      // both (two inlined copies of esc_load / eval_op cost the packed instantiation its fourth
+      // wave); cur is the marks left, or the walk's next slot.
+      const bool walk = __ballot(escm == ~0ull) != 0;
+      const uint32_t *const escv = LAG ? L.lag_ct : L.pk_vc;
+      for (uint64_t cur = walk ? off0 + lane : escm;;) {
+        uint64_t p;
+        if (walk) {
+          while (cur < off1 && escv[cur] != AM_PK_ESC) cur += WAVE;
+          if (cur >= off1) break;
+          p = cur, cur += WAVE;
+        } else {
+          if (!cur) break;
+          const uint32_t b = (uint32_t)__builtin_ctzll(cur);
+          cur &= cur - 1;
+          p = t0 + (uint64_t)(b / OPL) * TILE + (uint64_t)lane * OPL + b % OPL;
+        }
+        uint64_t sv[DMAX], ct;
+        uint32_t meta;
+        esc_load<DMAX>(L, nd, stride, p, LAG ? K : NONE, sv, ct, meta);
+        if (eval_op<DMAX, false>(u, meta, ct, sv, u.allmask, false, p, a) && !(meta & AM_META_BAD))
+          atomicOr(&ibm[p >> 5], 1u << (p & 31));
+      }
+      const uint32_t ecount = wave_sum_u32_v(a.count), eflags = wave_or_u32_v(a.flags);
+      const uint32_t epres = wave_or_u32_v(a.pres);
+      const uint64_t emex = wave_min_u64_v(a.min_excl);
+      uint64_t emx = 0;  // lane d: DC d's maximum over the included escaped ops
+#pragma unroll
+      for (int d = 0; d < DMAX; ++d) {
+        if (d >= (int)nd) continue;
+        const uint64_t am = wave_max_u64_v(a.mx[d]);
+        if ((uint32_t)d == lane) emx = am;
+      }
+      if (lane < nd) sm.ct[lane][j] = umax64(sm.ct[lane][j], emx);
+      if (lane == 0) {
+        sm.flags[j] |= eflags;
+        sm.count[j] += ecount;
+        sm.pres[j] |= epres;
+        sm.mex[j] = umin64(sm.mex[j], emex);
+      }
+    }
+    wave_sync();
+    // ---- the batch's outputs, derived from the merged partials: one coalesced store per column
+    //      (lane j: read b0 + j) ----
+    uint32_t ol = lane;  // (opaque, as sl_ above)
+    asm volatile("" : "+v"(ol));
+    if (ol < IWB && (((uint32_t)emask >> ol) & 1u)) {
+      const uint64_t r = sl[ol].r;
+      const uint32_t flags = sm.flags[ol];
+      const int32_t st = (flags & FLAG_BAD) ? AM_ERR_UNEXPECTED_OPERATION : AM_OK;
       R.status[r] = st;
-      R.flags[r] = (uint8_t)sm.flags[lane];
+      R.flags[r] = (uint8_t)(flags & 0xFFu);
       if (st == AM_OK) {
-        const uint32_t c = sm.count[lane];
-        R.new_last_op[r] = sm.nlo[lane];
+        const uint32_t c = sm.count[ol];
+        const uint32_t opres = c == 0 ? 0u : sm.pres[ol];  // (count 0: base ignore)
+        const uint64_t off0 = sl[ol].off0;
+        R.new_last_op[r] = new_last_op_b(L, sl[ol].idb, off0, off0 + sl[ol].nops, sm.mex[ol]);
         R.last_ct_ignore[r] = c == 0 ? 1 : 0;
-        R.last_ct_pres[r] = sm.pres[lane];
+        R.last_ct_pres[r] = opres;
         R.is_new_ss[r] = c > 0;
         R.count[r] = c;
 #pragma unroll
         for (int d = 0; d < DMAX; ++d)
-          if (d < (int)nd) R.last_ct[(uint64_t)d * n + r] = sm.ct[d][lane];
+          if (d < (int)nd) R.last_ct[(uint64_t)d * n + r] = ((opres >> d) & 1u) ? sm.ct[d][ol] : 0;
       }
     }
     wave_sync();  // the slots are rewritten by the next batch
@@ -2127,12 +2176,20 @@ int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_rea
   // the lag view when the log has it: 4 + 2 D bytes of commit vector per op instead of 4 D
   const bool lag = L->lag_ct && L->lag && L->key_lag;
   const bool spans = L->key_nspan && L->gspan && L->gsrc;
-  static int occ_i = 0, occ_w = 0, occ_s = 0;  // per kernel: each grid is sized by its own
-  if (!occ_i) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_i, k_grp_incl<D, TYPE, EXACT, true>, BLOCK, 0) !=
+  // per kernel: each grid is sized by its own (occ_i[LAG]: the two inclusion instantiations
+  // have their own launch bounds)
+  static int occ_i[2] = {0, 0}, occ_w = 0, occ_s = 0;
+  if (!occ_i[0]) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_i[0], k_grp_incl<D, TYPE, EXACT, false>, BLOCK, 0) !=
             hipSuccess ||
-        occ_i < 1)
-      occ_i = 2;
+        occ_i[0] < 1)
+      occ_i[0] = 2;
+  }
+  if (lag && !occ_i[1]) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_i[1], k_grp_incl<D, TYPE, EXACT, true>, BLOCK, 0) !=
+            hipSuccess ||
+        occ_i[1] < 1)
+      occ_i[1] = 2;
   }
   int &occ_r = spans ? occ_s : occ_w;  // the record pass that runs
   if (!occ_r) {
@@ -2141,9 +2198,18 @@ int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_rea
     if (e != hipSuccess || occ_r < 1) occ_r = 1;
   }
   const uint64_t want_i = (B->n_reads + NW * IWB - 1) / (NW * IWB), want_w = want_i;
-  const uint64_t bi = want_i < (uint64_t)ctx->n_cu * occ_i ? want_i : (uint64_t)ctx->n_cu * occ_i;
+  const uint64_t cap_p = (uint64_t)ctx->n_cu * occ_i[0], cap_l = (uint64_t)ctx->n_cu * occ_i[1];
+  const uint64_t bp = want_i < cap_p ? want_i : cap_p;          // the packed instantiation's grid
+  const uint64_t bi = lag ? (want_i < cap_l ? want_i : cap_l) : bp;  // the first launch's
   const uint64_t bw = want_w < (uint64_t)ctx->n_cu * occ_r ? want_w : (uint64_t)ctx->n_cu * occ_r;
   if (bi == 0) return AM_OK;
+  // the escape-mark rows of the inclusion pass: 64 lanes x 8 bytes per read slot of every wave of
+  // the larger grid (the two launches run one after the other and share them); a store without
+  // escaped ops never touches them
+  void *escv = nullptr;
+  if (int rc = am_ctx_scratch(ctx, AM_SCR_ESCM, (bi > bp ? bi : bp) * NW * IWB * WAVE * sizeof(uint64_t), &escv))
+    return rc;
+  uint64_t *const escr = (uint64_t *)escv;
   if (lag) {
     // the reads of packed-routed keys leave the lag instantiation through a list; the packed
     // instantiation takes exactly those (an empty list: its blocks return at once)
@@ -2151,12 +2217,12 @@ int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_rea
     am_sel rsel;
     if (int rc = am_route_list(ctx, B->n_reads, &routed, &rsel)) return rc;
     hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, true>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B, *R,
-                       S, next, routed, short_opl, (uint32_t *)ibm);
-    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B,
-                       *R, rsel, next, am_retry{}, short_opl, (uint32_t *)ibm);
+                       S, next, routed, short_opl, (uint32_t *)ibm, escr);
+    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bp), dim3(BLOCK), 0, ctx->stream, *L, *B,
+                       *R, rsel, next, am_retry{}, short_opl, (uint32_t *)ibm, escr);
   } else {
-    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B,
-                       *R, S, next, am_retry{}, short_opl, (uint32_t *)ibm);
+    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bp), dim3(BLOCK), 0, ctx->stream, *L, *B,
+                       *R, S, next, am_retry{}, short_opl, (uint32_t *)ibm, escr);
   }
   if (spans) {
     hipLaunchKernelGGL((k_grp_spans<D, TYPE>), dim3((unsigned)bw), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S,
