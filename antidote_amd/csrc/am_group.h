@@ -33,8 +33,9 @@
 //      wave ballots and their (a, b) pairs gathered into the output CSR -- already in the
 //      reference's order, no sort.
 // Reads with base-snapshot pairs, longer logs or ungrouped keys are handed to the next tier.
-// The split fresh read (k_grp_incl, then k_grp_spans) does step 2 over the group-span view: one
-// word per born group (birth op | kill op) instead of one record per birth and kill slot.
+// The split fresh read (am_group_split.h: k_grp_incl does step 1, then k_grp_spans steps 2 and 3)
+// does step 2 over the group-span view: one word per born group (birth op | kill op) instead of
+// one record per birth and kill slot; k_grp_recs stands in for a log without that view.
 #pragma once
 #include "am_block.h"
 #include "am_inclwin.h"
@@ -607,7 +608,8 @@ __device__ __forceinline__ bool base_ok(const am_op_log &L, const am_read_batch 
 
 // The wave tier takes a read (metadata mm, status ok): grouped within the LDS limits, its base
 // acceptable, and not a short read the lane tier takes next (short_opl != 0).  The inclusion
-// pass and the record pass of the split read (k_grp_incl, k_grp_wave<BM>) use the same test.
+// pass and the record passes of the split read (k_grp_incl, k_grp_spans / k_grp_recs) use the
+// same test.
 __device__ __forceinline__ bool wave_takes(const am_op_log &L, const am_read_batch &B, const GMeta &mm,
                                            uint32_t short_opl) {
   return !(mm.G == AM_NGRP_NONE || mm.G > VG || mm.off1 - mm.off0 > VOPS || !base_ok(L, B, mm.r) ||
@@ -795,9 +797,9 @@ __device__ bool base_merge(const am_op_log &L, const am_read_batch &B, am_read_r
   return true;
 }
 
-// BM (the split fresh read, after k_grp_incl): the inclusion bits come from the global bitmap
-// ibm (bit p = op slot p) and the scalar outputs are already written; this pass streams the
-// records and gathers the survivors only.
+// One pass per read: inclusion, records, scalar outputs and survivors.  (The fresh reads of a
+// store without a zone index at D <= 8 take the split read instead -- k_grp_incl, then
+// k_grp_spans / k_grp_recs, am_group_split.h -- see launch_d.)
 #ifndef AM_WAVE_FRESH_LAG
 #define AM_WAVE_FRESH_LAG 0
 #endif
@@ -807,10 +809,10 @@ __device__ bool base_merge(const am_op_log &L, const am_read_batch &B, am_read_r
 #ifndef AM_WAVE_WAVES
 #define AM_WAVE_WAVES 4  // waves per SIMD the wave tier is compiled for
 #endif
-template <int DMAX, int TYPE, bool GENERAL, bool PACKED, bool EXACT, bool BM = false>
+template <int DMAX, int TYPE, bool GENERAL, bool PACKED, bool EXACT>
 __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA, am_read_batch B, am_read_result R,
                                                                   am_sel S, am_retry next, uint32_t short_opl,
-                                                                  GrpHint H, const uint32_t *ibm = nullptr) {
+                                                                  GrpHint H) {
   const am_op_log L = LA.log();
   constexpr int OPL = vopl<DMAX, PACKED>();
   constexpr uint64_t TILE = (uint64_t)WAVE * OPL;
@@ -843,11 +845,9 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
       read_meta(L, B, S.idx ? (uint64_t)S.idx[sel0 + ii] : ii, TYPE, mm);
       rr = mm.r;
       if (mm.st != AM_OK) {
-        if (!BM) R.status[mm.r] = mm.st, R.flags[mm.r] = 0;
+        R.status[mm.r] = mm.st, R.flags[mm.r] = 0;
       } else if (!wave_takes(L, B, mm, short_opl)) {
-        hand = !BM;  // (short_opl: a short read the lane tier takes next; BM: handed on by k_grp_incl)
-      } else if (BM && R.status[mm.r] != AM_OK) {
-        // the inclusion pass ended the read (an invalid effect included)
+        hand = true;  // (short_opl: a short read the lane tier takes next)
       } else {
         elig = true;
         WSlot &w = s.slot[lane];
@@ -888,8 +888,8 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
       }
       // fresh reads over an exact-zone index stream tiles aligned to the zone blocks (a tile that
       // is one exact block is taken whole); the first tile masks the slots before off0
-      const bool zal = !BM && !GENERAL && PACKED && TILE == AM_ZONE_OPS && L.zone_vc && off1 - off0 >= AM_ZONE_OPS;
-      const uint64_t t0 = off0 & ~(uint64_t)((BM ? 32 : zal ? AM_ZONE_OPS : OPL) - 1);
+      const bool zal = !GENERAL && PACKED && TILE == AM_ZONE_OPS && L.zone_vc && off1 - off0 >= AM_ZONE_OPS;
+      const uint64_t t0 = off0 & ~(uint64_t)((zal ? AM_ZONE_OPS : OPL) - 1);
       const uint32_t sh = (uint32_t)(off0 - t0);
 
       // the first record chunk is in flight while the ops are evaluated (loaded after the zone
@@ -922,7 +922,7 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
       bool esc = false;  // some op of this lane did not fit the packed view
       // zone map: with a base snapshot (and no TxId), a tile whose zones are vectorclock:le the
       // base clock holds no candidate (belongs_to_snapshot_op/3) -- not streamed
-      const bool zskip = !BM && GENERAL && L.zone_vc && !u.base_ignore && !u.has_txid;
+      const bool zskip = GENERAL && L.zone_vc && !u.base_ignore && !u.has_txid;
       const uint64_t nz = (stride + AM_ZONE_OPS - 1) / AM_ZONE_OPS;
       // the read's zones in one round of loads: lane (d, z) tests zone z of DC d against the
       // base clock; a zone is inside the base when every DC's lane passes (reads spanning more
@@ -1020,11 +1020,7 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
         const uint64_t q = qa + (uint64_t)jj * 4 * WAVE + 4 * lane;
         rec[jj] = q < rk1 ? *(const u32x4 *)(L.rec_g + q) : u32x4{~0u, ~0u, ~0u, ~0u};
       }
-      if (BM) {  // the inclusion pass's bits of [t0, off1), word-aligned
-        const uint32_t nw = (uint32_t)((off1 - t0 + 31) / 32);
-        for (uint32_t i = lane; i < nw; i += WAVE) s.incl[i] = ibm[(t0 >> 5) + i];
-      }
-      for (uint64_t t = t0; !BM && t < off1; t += TILE) {
+      for (uint64_t t = t0; t < off1; t += TILE) {
         const uint64_t g = t + (uint64_t)lane * OPL;
         if (!GENERAL && zfull) {
           const uint32_t zi = (uint32_t)((t - t0) / AM_ZONE_OPS);
@@ -1067,7 +1063,7 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
         if (lane % LPW == 0) s.incl[(uint32_t)((t - t0) / 32) + lane / LPW] = word;
       }
       wave_sync();
-      const bool full = !BM && (!PACKED || __ballot(esc));
+      const bool full = !PACKED || __ballot(esc);
       if (PACKED && full) {  // rare: ops outside the packed view, through the escape reader
         esc_pass<DMAX, GENERAL>(L, nd, u, off0, off1, t0, stride, lane, WAVE, s.incl, a, lr.on ? L.lag_ct : L.pk_vc,
                                 lr.on ? pk.K : NONE);
@@ -1112,9 +1108,7 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
       // ---- 3. scalar outputs (VGPR wave reductions) ----
       uint32_t count = 0, flags = 0, pres = 0;
       uint64_t min_excl = NONE, mxl = 0;
-      if (!BM)
-        wave_scalars<DMAX, PACKED>(ap, a, full, PACKED ? pk.K : 0, u.allmask, nd, lane, count, flags, pres, min_excl,
-                                   mxl);
+      wave_scalars<DMAX, PACKED>(ap, a, full, PACKED ? pk.K : 0, u.allmask, nd, lane, count, flags, pres, min_excl, mxl);
       int32_t status = (flags & FLAG_BAD) ? AM_ERR_UNEXPECTED_OPERATION : AM_OK;
       const bool ign = u.base_ignore && count == 0;
       const uint32_t opres = ign ? 0u : (pres | u.cpres);
@@ -1166,14 +1160,6 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
         if (ns > ocap) status = AM_ERR_CAPACITY;
       }
       PH(4);
-      if (BM) {  // the inclusion pass wrote the scalar outputs
-        if (lane == 0) {
-          if (status == AM_OK) R.value.set_len[r] = ns;
-          else R.status[r] = status;
-        }
-        wave_sync();
-        continue;
-      }
       if (status == AM_OK && lane < nd) R.last_ct[(uint64_t)lane * B.n_reads + r] = myct;
       if (lane == 0) {
         R.status[r] = status;
@@ -1199,807 +1185,20 @@ __global__ void __launch_bounds__(BLOCK, AM_WAVE_WAVES) k_grp_wave(am_log_arg LA
   PH_END();
 }
 
-// ---------------------------------------------------------------- split fresh read, pass 1
-// A fresh read (the batch clock, no base, no TxId; packed view, no zone index) in two passes:
-// k_grp_incl streams the read's commit vectors -- 256-op tiles, one 16-byte load per DC and lane,
-// the wave's only live state the tile and the partials -- and writes its inclusion bits into the
-// global bitmap ibm (bit p = op slot p) and its scalar outputs {NewLastOp, LastOpCt, IsNewSS,
-// Count, status}; k_grp_wave<BM> then streams the records against those bits and gathers the
-// survivors.  A wave takes 32 CONSECUTIVE reads at a time and their scalar outputs leave through
-// LDS as one coalesced store per column (single-lane stores of reads far apart write partial
-// lines of the output columns, each line written back once per writer).  Ops outside the
-// streamed view (escaped ops, rare) are evaluated once per batch, after its reads' tile loops:
-// a read that met any leaves its lanes' escape marks in a scratch row (escr: 512 bytes per read
-// slot of the wave, written for such reads only) and its in-view partials in the LDS rows, and
-// the deferred phase ORs the included escaped ops into the bitmap and merges their partials in
-// before the outputs are derived.
-constexpr uint32_t IWB = 32;  // reads per wave batch
-__device__ __forceinline__ uint32_t wave_min_u32_v(uint32_t v) {
-#define S_(C) v = min(v, dpp32<C>(v));
-  AMK_ROW_STEPS(S_)
-#undef S_
-  v = min(v, (uint32_t)__shfl_xor((int)v, 16, WAVE));
-  return min(v, (uint32_t)__shfl_xor((int)v, 32, WAVE));
-}
-struct ISlot {
-  uint64_t off0, K, idb, key;
-  uint32_t r, nops;
-};
-template <int DMAX>
-struct ISmem {
-  ISlot slot[IWB];
-  uint32_t mx[DMAX][WAVE];      // one read's per-lane LastOpCt maxima, transposed for the reduction
-  // the batch's partials, by read: the in-view values as the tile loop leaves them, then merged
-  // with the escaped ops' (the deferred phase); the outputs are derived from them once, as the
-  // batch leaves
-  uint64_t ct[DMAX][IWB];       // LastOpCt maxima, not yet masked by the presence
-  uint64_t mex[IWB];            // the first excluded op's slot (NONE: none)
-  uint32_t count[IWB], pres[IWB];
-  uint32_t flags[IWB];          // with FLAG_BAD
-};
-
-// ops [g, g + OPL) of the lane (OPL consecutive slots, g OPL-aligned), their entries x those of
-// the packed view (pk_ent) or rebuilt from the lag view where they are used (lag_ent, am_wave.h):
-// inclusion bits (is_op_in_snapshot/7 against the batch clock: every entry X[d] - K <= S[d] - K)
-// and the partials.  RANGE: the tile may hold slots outside [off0, off1); escaped ops
-// (x.esc(k) == AM_PK_ESC) are left to the caller (esc bit k).
-template <int DMAX, int OPL, bool RANGE, class Ent>
-__device__ __forceinline__ uint32_t incl_tile(const Ent &x, const PkRead<DMAX> &pk, uint64_t g, uint64_t off0,
-                                              uint64_t off1, uint32_t (&mx)[DMAX], uint32_t &esc, uint32_t &cand) {
-  uint32_t ib = 0;
-#pragma unroll
-  for (int k = 0; k < OPL; ++k) {
-    const bool e = x.esc(k) == AM_PK_ESC;
-    const bool inr = !RANGE || (g + k >= off0 && g + k < off1);
-    bool in = inr && !e;
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) in = in && x(k, d) <= pk.thr[d];
-    esc |= (uint32_t)(inr && e) << k;
-    cand |= (uint32_t)(inr && !e) << k;
-    if (in) {
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) mx[d] = max(mx[d], x(k, d));
-    }
-    ib |= (uint32_t)in << k;
-  }
-  return ib;
+// The grid of a grid-stride launch: `want` blocks, capped by what the device holds at once, n_cu
+// times the kernel's blocks per CU (queried once into the caller's occ; `fallback` when the
+// query fails).
+template <class K>
+uint64_t grp_grid(const am_ctx *ctx, int &occ, K kernel, int block, size_t smem, int fallback, uint64_t want) {
+  if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, smem) != hipSuccess || occ < 1))
+    occ = fallback;
+  const uint64_t cap = (uint64_t)ctx->n_cu * occ;
+  return want < cap ? want : cap;
 }
 
-// the same test for the ops of the lane that the commit word left undecided (bits of win, the
-// window of am_inclwin.h): ops outside win neither pass here nor touch the maxima
-template <int DMAX, int OPL, class Ent>
-__device__ __forceinline__ uint32_t incl_tile_w(const Ent &x, const PkRead<DMAX> &pk, uint32_t win,
-                                                uint32_t (&mx)[DMAX]) {
-  uint32_t ib = 0;
-#pragma unroll
-  for (int k = 0; k < OPL; ++k) {
-    bool in = (win >> k) & 1u;
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) in = in && x(k, d) <= pk.thr[d];
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) mx[d] = max(mx[d], in ? x(k, d) : 0u);
-    ib |= (uint32_t)in << k;
-  }
-  return ib;
-}
-
-// LAG: the read streams the lag view (am_op_log.lag_ct / lag / key_lag, 4 + 2 D bytes per op)
-// and rebuilds each packed entry X[d] - K = lag_ct - key_lag[d] - lag[d] in u32 (exact: the entry
-// fits u32 for every op the view holds); else the packed view (4 D bytes per op)
-//
-// Waves per SIMD, by clock width D.  The pass is bound by the chain of dependent loads of a read
-// (lag bases and newest commit words, then each window tile's lag lines), which more waves
-// cover.  The per-read loop holds the tile loop and the reduction only: escaped ops are
-// evaluated after the batch's loop, where no tile state is live, and what the batch's set-up
-// and outputs derive from the lane number is computed per batch (sl_, ol), so neither weighs on
-// the tile loop's registers.  LAG (two tiles of commit words, the lag words of one, the window
-// state): 95-96 VGPRs at D = 8, five waves without a vector spill.  Packed (the tile's D x 4
-// entries): 103 VGPRs at D = 8, four waves (fifteen spilled at five).
-#ifndef AM_INCL_WAVES
-#define AM_INCL_WAVES(D) 4
-#endif
-#ifndef AM_INCL_LAG_WAVES
-#define AM_INCL_LAG_WAVES(D) 5
-#endif
-template <int DMAX, int TYPE, bool EXACT, bool LAG>
-__global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL_WAVES(DMAX)) k_grp_incl(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
-                                                       am_retry next, am_retry routed, uint32_t short_opl,
-                                                       uint32_t *ibm, uint64_t *escr) {
-  const am_op_log L = LA.log();
-  constexpr int OPL = 4;
-  constexpr uint64_t TILE = (uint64_t)WAVE * OPL;
-  constexpr uint32_t LPW = 32 / OPL;
-  __shared__ ISmem<DMAX> smem[NW];
-  ISmem<DMAX> &sm = smem[threadIdx.x >> 6];
-  ISlot *sl = sm.slot;
-  const uint32_t lane = threadIdx.x & (WAVE - 1);
-  const uint32_t nd = EXACT ? (uint32_t)DMAX : L.n_dc;
-  const uint64_t stride = L.snap_stride ? L.snap_stride : L.n_ops;
-  const uint32_t sel0 = S.idx ? uniform_u32(S.range[0]) : 0u;
-  const uint64_t nsel = S.idx ? (uint64_t)(uniform_u32(S.range[1]) - sel0) : B.n_reads;
-  const uint64_t W = (uint64_t)gridDim.x * NW;
-  const uint64_t gw = (uint64_t)blockIdx.x * NW + uniform_u32(threadIdx.x >> 6);
-  const uint64_t n = B.n_reads;
-  ReadU<DMAX> u;
-  read_inputs<DMAX, false, true>(L, nd, B, 0, u);  // one clock, no bases / TxIds
-
-  for (uint64_t b0 = gw * IWB; b0 < nsel; b0 += (uint64_t)IWB * W) {
-    // ---- lane j < IWB: read b0 + j -> slot j (errors and hand-offs leave here) ----
-    // (sl_: the lane number, opaque to the compiler -- what the batch's set-up and outputs derive
-    //  from it is computed where it is used, per batch, not once per kernel and then held in
-    //  registers across the tile loop, whose budget has no room for it)
-    uint32_t sl_ = lane, sopl = short_opl;  // (sopl: the same for the mask wave_takes makes of it)
-    asm volatile("" : "+v"(sl_));
-    asm volatile("" : "+s"(sopl));
-    const uint64_t ii = b0 + sl_;
-    bool elig = false, hand = false, route = false;
-    uint64_t rr = 0;
-    if (sl_ < IWB && ii < nsel) {
-      GMeta mm;
-      read_meta(L, B, S.idx ? (uint64_t)S.idx[sel0 + ii] : ii, TYPE, mm);
-      rr = mm.r;
-      if (mm.st != AM_OK) {
-        R.status[mm.r] = mm.st, R.flags[mm.r] = 0;
-      } else if (!wave_takes(L, B, mm, sopl)) {
-        hand = true;
-      } else if (LAG && routed.list && L.key_lag[mm.key * nd] == AM_LAG_ROUTED) {
-        route = true;  // a packed-routed key: the packed instantiation's (launch_split)
-      } else {
-        elig = true;
-        ISlot &w = sl[sl_];
-        w.off0 = mm.off0, w.K = L.key_tbase[mm.key], w.idb = L.key_id_base ? L.key_id_base[mm.key] : 1;
-        w.key = mm.key;
-        w.r = (uint32_t)mm.r, w.nops = (uint32_t)(mm.off1 - mm.off0);
-      }
-    }
-    const uint64_t hm = __ballot(hand);
-    if (hm) {
-      uint32_t base = 0;
-      if (sl_ == 0) base = atomicAdd(next.count, (uint32_t)__popcll(hm));
-      base = uniform_u32(base);
-      if (hand) next.list[base + (uint32_t)__popcll(hm & ((1ull << sl_) - 1ull))] = (uint32_t)rr;
-    }
-    if (LAG) retry_append(routed, route, (uint32_t)rr, sl_);
-    const uint64_t emask = __ballot(elig);
-    uint32_t escmask = 0;  // the batch's reads with escaped ops (wave-uniform): the deferred phase's
-    uint64_t *const escw = escr + (gw * IWB) * WAVE;  // this wave's escape-mark rows, one per slot
-    wave_sync();
-
-    for (uint64_t em = emask; em; em &= em - 1) {
-      const uint32_t j = (uint32_t)__builtin_ctzll(em);
-      const uint64_t off0 = uniform_u64(sl[j].off0), off1 = off0 + uniform_u32(sl[j].nops);
-      PkRead<DMAX> pk;
-      pk_setup(u, nd, uniform_u64(sl[j].K), pk);
-      uint32_t mx[DMAX], lb[DMAX];  // lb: the key's lag bases (LAG)
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) mx[d] = 0;
-      if (LAG) {
-        const uint64_t key = uniform_u64(sl[j].key);
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) lb[d] = uniform_u32(d < (int)nd ? (uint32_t)L.key_lag[key * nd + d] : 0u);
-      }
-      uint32_t cnt = 0, minex = 0xFFFFFFFFu, anyc = 0, anyesc = 0;
-      uint64_t escm = 0;  // the lane's escaped ops: bit OPL * tile + k (the first 64 / OPL tiles)
-      const uint64_t t0 = off0 & ~31ull;  // 32-op aligned: lane groups of LPW fill whole bitmap words
-      // one tile's inclusion bits -> partials, escape marks and the bitmap words
-      auto tile_out = [&](uint64_t t, uint64_t g, uint32_t ib, uint32_t esc, uint32_t cand) {
-        if (pk.never) ib = 0;
-        cnt += (uint32_t)__popc(ib);
-        anyc |= cand;
-        anyesc |= esc;
-        const uint64_t ti = (t - t0) / TILE;
-        if (esc) escm |= ti < 64 / OPL ? (uint64_t)esc << (OPL * ti) : ~0ull;  // ~0: walk the key
-        const uint32_t ex = cand & ~ib;
-        if (ex) minex = min(minex, (uint32_t)(g - t0) + (uint32_t)__builtin_ctz(ex));
-        uint32_t word = ib << (OPL * (lane % LPW));
-#pragma unroll
-        for (uint32_t xo = 1; xo < LPW; xo <<= 1) word |= (uint32_t)__shfl_xor((int)word, (int)xo);
-        const uint64_t w0 = g & ~31ull;  // this lane group's word: ops [w0, w0 + 32)
-        if (lane % LPW == 0 && w0 < off1) {
-          if (w0 >= off0 && w0 + 32 <= off1) {
-            ibm[w0 >> 5] = word;
-          } else {  // a word shared with a neighbouring key: only this read's bits change
-            const uint32_t lo = off0 > w0 ? (uint32_t)(off0 - w0) : 0u;
-            const uint32_t hi = off1 < w0 + 32 ? (uint32_t)(off1 - w0) : 32u;
-            const uint32_t mask = (hi >= 32 ? ~0u : ((1u << hi) - 1u)) & ~((1u << lo) - 1u);
-            atomicAnd(ibm + (w0 >> 5), ~mask);
-            atomicOr(ibm + (w0 >> 5), word & mask);
-          }
-        }
-      };
-      if constexpr (LAG) {
-        static_assert(OPL == 4, "four u16 lags per 8-byte load");
-        // The commit word alone decides most ops (am_inclwin.h): only ops in the window
-        // in_lim <= c < out_lim load their lags.  Tiles are walked newest first, so the newest
-        // included ops raise cmax (and with it in_lim) before the older ones are met; the commit
-        // words of tile t - 1 are in flight while tile t is evaluated (two register sets, no
-        // copies between them).  A whole tile the limits decide takes a short path (tile_const).
-        int64_t cinf = AM_IW_NOBOUND;
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d)
-          if (d < (int)nd) cinf = am_iw_fold(cinf, pk.thr[d], lb[d]);
-        am_inclwin iw;
-        am_iw_init(&iw, cinf, pk.never);
-        const uint32_t cin_lim = am_iw_lim(iw.cin), out_lim = am_iw_lim(iw.hi);
-        uint32_t in_lim = am_iw_in_lim(&iw);
-        uint32_t cA[OPL], cB[OPL];
-        auto load = [&](uint64_t t, uint32_t (&c)[OPL]) {
-          const uint64_t g = t + (uint64_t)lane * OPL;
-#pragma unroll
-          for (int k = 0; k < OPL; ++k) c[k] = 0;
-          if (g < off1) ld_n32<OPL>(L.lag_ct + g, c);
-        };
-        // a whole tile of included ops below every maximum, or of excluded ops: no shuffles
-        auto tile_const = [&](uint64_t g, bool in) {
-          if (in) cnt += OPL;
-          else minex = min(minex, (uint32_t)(g - t0));
-          anyc |= (1u << OPL) - 1u;
-          if (lane % LPW == 0) ibm[g >> 5] = in ? ~0u : 0u;  // every word lies inside the read
-        };
-        auto eval = [&](uint64_t t, const uint32_t (&c)[OPL]) {
-          const uint64_t g = t + (uint64_t)lane * OPL;
-          const bool whole = t >= off0 && t + TILE <= off1;
-          if (whole) {
-            static_assert(OPL == 4, "min / max of four words");
-            const uint32_t ch = max(max(c[0], c[1]), max(c[2], c[3]));  // (AM_PK_ESC is the largest word)
-            if (!__ballot(ch >= in_lim)) return tile_const(g, true);
-            const uint32_t cl = min(min(c[0], c[1]), min(c[2], c[3]));
-            if (!__ballot(cl < out_lim || ch == AM_PK_ESC)) return tile_const(g, false);
-          }
-          uint32_t esc = 0, cand = 0, sure = 0;  // sure: 1 + the lane's largest c <= cin
-#pragma unroll
-          for (int k = 0; k < OPL; ++k) {
-            const bool e = c[k] == AM_PK_ESC;
-            const bool inr = whole || (g + k >= off0 && g + k < off1);
-            esc |= (uint32_t)(inr && e) << k;
-            cand |= (uint32_t)(inr && !e) << k;
-            if (inr && c[k] < cin_lim) sure = max(sure, c[k] + 1u);
-          }
-          // the bound without loads, before this tile's own ops are classified
-          if (in_lim < cin_lim) {
-            const uint32_t m = uniform_u32(wave_max_u32_v(sure));
-            if (m) am_iw_raise(&iw, am_iw_cmax_sure(m - 1u)), in_lim = am_iw_in_lim(&iw);
-          }
-          uint32_t ib = 0, win = 0;
-#pragma unroll
-          for (int k = 0; k < OPL; ++k) {
-            const int cl = am_iw_class32(c[k], in_lim, out_lim);
-            ib |= (uint32_t)(cl == AM_IW_IN) << k;
-            win |= (uint32_t)(cl == AM_IW_WINDOW) << k;
-          }
-          ib &= cand, win &= cand;
-          if (__ballot(win != 0)) {  // lanes with an op in the window: a predicated 8-byte load per DC
-            uint32_t lw[DMAX][2];
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) {
-              uint2 v = {0, 0};
-              if (d < (int)nd && win) v = *(const uint2 *)(L.lag + (uint64_t)d * stride + g);
-              lw[d][0] = v.x, lw[d][1] = v.y;
-            }
-            // (pad DCs d >= nd: c - lb[d] with lb = 0 lies under the always-passing pad threshold)
-            const uint32_t iwb = incl_tile_w<DMAX, OPL>(lag_ent(c, lw, lb), pk, win, mx);
-            ib |= iwb;
-            if (__ballot(iwb != 0)) {  // any lane's maxima bound every lane's
-              int64_t v = AM_IW_NOBOUND;
-#pragma unroll
-              for (int d = 0; d < DMAX; ++d)
-                if (d < (int)nd) v = am_iw_fold(v, mx[d], lb[d]);
-              constexpr int64_t BIAS = 1ll << 32;  // v >= INT32_MIN: unsigned order
-              am_iw_raise(&iw, (int64_t)uniform_u64(wave_max_u64_v((uint64_t)(v + BIAS))) - BIAS);
-              in_lim = am_iw_in_lim(&iw);
-            }
-          }
-          tile_out(t, g, ib, esc, cand);
-        };
-        const uint64_t tl = t0 + (off1 - 1 - t0) / TILE * TILE;  // the last tile
-        load(tl, cA);
-        for (uint64_t t = tl;; t -= 2 * TILE) {
-          if (t > t0) load(t - TILE, cB);
-          eval(t, cA);
-          if (t == t0) break;
-          if (t - TILE > t0) load(t - 2 * TILE, cA);
-          eval(t - TILE, cB);
-          if (t - TILE == t0) break;
-        }
-      } else {
-        for (uint64_t t = t0; t < off1; t += TILE) {
-          const uint64_t g = t + (uint64_t)lane * OPL;
-          uint32_t esc = 0, cand = 0;
-          const bool whole = t >= off0 && t + TILE <= off1;
-          uint32_t x[OPL][DMAX];
-#pragma unroll
-          for (int d = 0; d < DMAX; ++d) {
-            uint32_t q[OPL] = {};
-            if (d < (int)nd && g < off1) ld_n32<OPL>(L.pk_vc + (uint64_t)d * stride + g, q);
-#pragma unroll
-            for (int k = 0; k < OPL; ++k) x[k][d] = q[k];
-          }
-          const uint32_t ib = whole ? incl_tile<DMAX, OPL, false>(pk_ent(x), pk, g, off0, off1, mx, esc, cand)
-                                    : incl_tile<DMAX, OPL, true>(pk_ent(x), pk, g, off0, off1, mx, esc, cand);
-          tile_out(t, g, ib, esc, cand);
-        }
-      }
-      // ---- the read's scalar outputs: LastOpCt maxima reduced through LDS (lane 8 d + c takes
-      //      DC d's entries of lanes 8 c .. 8 c + 7, then an 8-lane max), the rest by DPP ----
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) sm.mx[d][lane] = mx[d];
-      const uint32_t count_p = wave_sum_u32_v(cnt);
-      minex = wave_min_u32_v(minex);
-      const bool cands = __ballot(anyc != 0) != 0;
-      const bool escs = __ballot(anyesc != 0) != 0;
-      wave_sync();
-      uint32_t m = 0;
-      {
-        const uint32_t d = lane >> 3, c = lane & 7u;
-        if (d < (uint32_t)DMAX) {
-          const u32x4 a0 = *(const u32x4 *)&sm.mx[d][8 * c], a1 = *(const u32x4 *)&sm.mx[d][8 * c + 4];
-          m = max(max(max(a0.x, a0.y), max(a0.z, a0.w)), max(max(a1.x, a1.y), max(a1.z, a1.w)));
-        }
-        // lanes ^ 1, ^ 2, then the other quad of the eight (row_half_mirror): no lane addresses,
-        // which the compiler would compute once per batch and hold across the tile loop
-        m = max(m, dpp32<0xB1>(m));
-        m = max(m, dpp32<0x4E>(m));
-        m = max(m, dpp32<0x141>(m));
-      }
-      // lane d: DC d's packed maximum (relative to K), from lane 8 d (its address from the opaque
-      // lane number, for the same reason)
-      uint32_t ql = lane;
-      asm volatile("" : "+v"(ql));
-      const uint32_t mxd = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((ql & 7u) << 5), (int)m);
-      // the read's in-view partials into the batch's LDS rows (slot j).  Ops outside the streamed
-      // view (rare) are not evaluated here: the read leaves its lanes' escape marks in the wave's
-      // scratch row j and its bit in escmask, and the deferred phase below merges them in
-      if (lane < nd) sm.ct[lane][j] = count_p ? pk.K + mxd : 0;
-      if (lane == 0) {
-        sm.flags[j] = cands ? pk.miss : 0u;
-        sm.count[j] = count_p;
-        sm.pres[j] = count_p ? u.allmask : 0u;
-        sm.mex[j] = minex == 0xFFFFFFFFu ? NONE : t0 + minex;
-      }
-      if (escs) {
-        escw[(uint64_t)j * WAVE + lane] = escm;
-        escmask |= 1u << j;
-      }
-      wave_sync();  // sm.mx is rewritten by the next read
-    }
-    // ---- the deferred phase: the escaped ops of the batch's reads that met any, through the
-    //      escape reader; the included ones' bits are ORed into the bitmap and their partials
-    //      merged into the read's row.  No tile state is live here, so the D-wide u64 values of
-    //      esc_load / eval_op do not weigh on the tile loop's registers ----
-    if (escmask) __builtin_amdgcn_s_waitcnt(0);  // the batch's bitmap words and mark rows are out
-    for (uint32_t xm = escmask; xm; xm &= xm - 1) {
-      const uint32_t j = (uint32_t)__builtin_ctz(xm);
-      const uint64_t off0 = uniform_u64(sl[j].off0), off1 = off0 + uniform_u32(sl[j].nops);
-      const uint64_t K = uniform_u64(sl[j].K), t0 = off0 & ~31ull;
-      const uint64_t escm = escw[(uint64_t)j * WAVE + lane];
-      Acc<DMAX> a;
-      a.reset();
-      // The lane's own escaped ops, marked by the tile loop: no second walk of the key.  A long
-      // key's late tiles have no mark bits (a lane's ~0): the wave walks the escape marks of the
-      // view it streamed instead, lane l the slots off0 + l, + 64, ...  One evaluation site serves
-      // both (two inlined copies of esc_load / eval_op cost the packed instantiation its fourth
-      // wave); cur is the marks left, or the walk's next slot.
-      const bool walk = __ballot(escm == ~0ull) != 0;
-      const uint32_t *const escv = LAG ? L.lag_ct : L.pk_vc;
-      for (uint64_t cur = walk ? off0 + lane : escm;;) {
-        uint64_t p;
-        if (walk) {
-          while (cur < off1 && escv[cur] != AM_PK_ESC) cur += WAVE;
-          if (cur >= off1) break;
-          p = cur, cur += WAVE;
-        } else {
-          if (!cur) break;
-          const uint32_t b = (uint32_t)__builtin_ctzll(cur);
-          cur &= cur - 1;
-          p = t0 + (uint64_t)(b / OPL) * TILE + (uint64_t)lane * OPL + b % OPL;
-        }
-        uint64_t sv[DMAX], ct;
-        uint32_t meta;
-        esc_load<DMAX>(L, nd, stride, p, LAG ? K : NONE, sv, ct, meta);
-        if (eval_op<DMAX, false>(u, meta, ct, sv, u.allmask, false, p, a) && !(meta & AM_META_BAD))
-          atomicOr(&ibm[p >> 5], 1u << (p & 31));
-      }
-      const uint32_t ecount = wave_sum_u32_v(a.count), eflags = wave_or_u32_v(a.flags);
-      const uint32_t epres = wave_or_u32_v(a.pres);
-      const uint64_t emex = wave_min_u64_v(a.min_excl);
-      uint64_t emx = 0;  // lane d: DC d's maximum over the included escaped ops
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) {
-        if (d >= (int)nd) continue;
-        const uint64_t am = wave_max_u64_v(a.mx[d]);
-        if ((uint32_t)d == lane) emx = am;
-      }
-      if (lane < nd) sm.ct[lane][j] = umax64(sm.ct[lane][j], emx);
-      if (lane == 0) {
-        sm.flags[j] |= eflags;
-        sm.count[j] += ecount;
-        sm.pres[j] |= epres;
-        sm.mex[j] = umin64(sm.mex[j], emex);
-      }
-    }
-    wave_sync();
-    // ---- the batch's outputs, derived from the merged partials: one coalesced store per column
-    //      (lane j: read b0 + j) ----
-    uint32_t ol = lane;  // (opaque, as sl_ above)
-    asm volatile("" : "+v"(ol));
-    if (ol < IWB && (((uint32_t)emask >> ol) & 1u)) {
-      const uint64_t r = sl[ol].r;
-      const uint32_t flags = sm.flags[ol];
-      const int32_t st = (flags & FLAG_BAD) ? AM_ERR_UNEXPECTED_OPERATION : AM_OK;
-      R.status[r] = st;
-      R.flags[r] = (uint8_t)(flags & 0xFFu);
-      if (st == AM_OK) {
-        const uint32_t c = sm.count[ol];
-        const uint32_t opres = c == 0 ? 0u : sm.pres[ol];  // (count 0: base ignore)
-        const uint64_t off0 = sl[ol].off0;
-        R.new_last_op[r] = new_last_op_b(L, sl[ol].idb, off0, off0 + sl[ol].nops, sm.mex[ol]);
-        R.last_ct_ignore[r] = c == 0 ? 1 : 0;
-        R.last_ct_pres[r] = opres;
-        R.is_new_ss[r] = c > 0;
-        R.count[r] = c;
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d)
-          if (d < (int)nd) R.last_ct[(uint64_t)d * n + r] = ((opres >> d) & 1u) ? sm.ct[d][ol] : 0;
-      }
-    }
-    wave_sync();  // the slots are rewritten by the next batch
-  }
-}
-
-// ---------------------------------------------------------------- split fresh read, pass 2
-// k_grp_recs: the records of the reads k_grp_incl took, against its bitmap, and the survivors'
-// pairs.  Latency-bound (a read is a few KB), so a wave keeps the NEXT read's bitmap words and
-// first two record chunks in flight while it applies this read's records and gathers its
-// survivors; LDS per wave is a few KB (survivor list in rounds), so ~5 waves per SIMD.
-constexpr uint32_t RCH = 512;    // records per chunk: two 16-byte loads per lane
-constexpr uint32_t RLIST = 256;  // survivor-list entries per gather round
-struct RSlot {
-  uint64_t off0, rk0, ooff;
-  uint32_t r, nops, nrec, G, ocap, ok;
-};
-struct RSmem {
-  uint32_t born[VG / 32], killed[VG / 32];
-  uint32_t incl[VWORDS];
-  uint16_t list[RLIST];
-  uint16_t bri[VG];  // per group: its birth record (from the read's rk0), set with its born bit
-  RSlot slot[IWB];
-};
-struct RPre {  // a read's prefetched inputs: one bitmap word and two record chunks per lane
-  uint32_t w;
-  u32x4 c[4];
-};
-// The record rule of a fresh read, one record: x (record i of its read, 0xFFFFFFFF: a dead slot)
-// against the read's LDS bitmap (bit = op + sh) sets its group's born or killed bit, a birth
-// also the group's birth record.  (k_grp_recs, and k_grp_spans for its keys without spans.)
-__device__ __forceinline__ void rec_apply(uint32_t x, uint32_t i, uint32_t sh, const uint32_t *incl, uint32_t *born,
-                                          uint32_t *killed, uint16_t *bri) {
-  if (x == 0xFFFFFFFFu) return;
-  const uint32_t bit = AM_REC_OP(x) + sh;
-  if (!((incl[bit >> 5] >> (bit & 31)) & 1u)) return;
-  const uint32_t g = AM_REC_GRP(x);
-  atomicOr(((x & AM_REC_KILL) ? killed : born) + (g >> 5), 1u << (g & 31));
-  if (!(x & AM_REC_KILL)) bri[g] = (uint16_t)i;  // a group's one birth
-}
-
-template <int DMAX, int TYPE>
-__global__ void __launch_bounds__(BLOCK, 5) k_grp_recs(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
-                                                       uint32_t short_opl, const uint32_t *ibm) {
-  const am_op_log L = LA.log();
-  __shared__ RSmem smem[NW];
-  RSmem &s = smem[threadIdx.x >> 6];
-  const uint32_t lane = threadIdx.x & (WAVE - 1);
-  const uint32_t sel0 = S.idx ? uniform_u32(S.range[0]) : 0u;
-  const uint64_t nsel = S.idx ? (uint64_t)(uniform_u32(S.range[1]) - sel0) : B.n_reads;
-  const uint64_t W = (uint64_t)gridDim.x * NW;
-  const uint64_t gw = (uint64_t)blockIdx.x * NW + uniform_u32(threadIdx.x >> 6);
-  const uint64_t *const pairs = L.prec ? L.prec : L.grp;
-
-  // prefetch read j of the slot table: bitmap words [t0 / 32, ...) (lane i: word i, the first
-  // 64), records [rk0 & ~3, + 2 RCH)
-  auto pre = [&](uint32_t j, RPre &p) {
-    const uint64_t off0 = s.slot[j].off0, rk0 = s.slot[j].rk0;
-    const uint32_t nops = s.slot[j].nops, nrec = s.slot[j].nrec;
-    const uint64_t t0 = off0 & ~31ull, rk1 = rk0 + nrec;
-    const uint32_t nw = (uint32_t)((off0 + nops - t0 + 31) / 32);
-    p.w = lane < nw ? ibm[(t0 >> 5) + lane] : 0u;
-    const uint64_t qa = rk0 & ~3ull;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const uint64_t q = qa + (uint64_t)c * 4 * WAVE + 4 * lane;
-      p.c[c] = q < rk1 ? *(const u32x4 *)(L.rec_g + q) : u32x4{~0u, ~0u, ~0u, ~0u};
-    }
-  };
-  // records [q, q + 4) against the LDS bitmap (bit = op + sh) -> born / killed bits
-  auto apply4 = [&](u32x4 v, uint64_t q, uint64_t rk0, uint64_t rk1, uint32_t sh) {
-    const uint32_t xs[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (xs[k] == 0xFFFFFFFFu || q + k < rk0 || q + k >= rk1) continue;
-      rec_apply(xs[k], (uint32_t)(q + k - rk0), sh, s.incl, s.born, s.killed, s.bri);
-    }
-  };
-
-  for (uint64_t b0 = gw * IWB; b0 < nsel; b0 += (uint64_t)IWB * W) {
-    // ---- lane j < IWB: read b0 + j -> slot j (the reads k_grp_incl took and left ok) ----
-    const uint64_t ii = b0 + lane;
-    bool ok = false;
-    if (lane < IWB && ii < nsel) {
-      GMeta mm;
-      read_meta(L, B, S.idx ? (uint64_t)S.idx[sel0 + ii] : ii, TYPE, mm);
-      ok = mm.st == AM_OK && wave_takes(L, B, mm, short_opl) && R.status[mm.r] == AM_OK;
-      if (ok) {
-        RSlot &w = s.slot[lane];
-        const uint64_t o0 = R.value.set_off[mm.r], o1 = R.value.set_off[mm.r + 1];
-        w.off0 = mm.off0, w.rk0 = mm.rk0, w.ooff = o0;
-        w.r = (uint32_t)mm.r, w.nops = (uint32_t)(mm.off1 - mm.off0), w.nrec = (uint32_t)(mm.rk1 - mm.rk0);
-        w.G = mm.G, w.ocap = o1 - o0 < 0xFFFFFFFFull ? (uint32_t)(o1 - o0) : 0xFFFFFFFFu;
-      }
-    }
-    uint64_t em = __ballot(ok);
-    wave_sync();
-    RPre cur;
-    if (em) pre((uint32_t)__builtin_ctzll(em), cur);
-    uint32_t setlen = 0;  // lane j: read j's survivor count
-    int32_t cap_err = 0;  // lane j: read j overflowed its capacity
-    for (; em; em &= em - 1) {
-      const uint32_t j = (uint32_t)__builtin_ctzll(em);
-      const uint64_t off0 = uniform_u64(s.slot[j].off0), rk0 = uniform_u64(s.slot[j].rk0);
-      const uint64_t off1 = off0 + uniform_u32(s.slot[j].nops), rk1 = rk0 + uniform_u32(s.slot[j].nrec);
-      const uint32_t G = uniform_u32(s.slot[j].G);
-      const uint64_t t0 = off0 & ~31ull;
-      const uint32_t sh = (uint32_t)(off0 - t0), nw = (uint32_t)((off1 - t0 + 31) / 32);
-      // this read's bitmap into LDS (words past the first 64 straight from memory: long logs)
-      if (lane < nw) s.incl[lane] = cur.w;
-      for (uint32_t i = WAVE + lane; i < nw; i += WAVE) s.incl[i] = ibm[(t0 >> 5) + i];
-      for (uint32_t g = lane; g < (G + 31) / 32; g += WAVE) s.born[g] = 0, s.killed[g] = 0;
-      u32x4 c[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) c[k] = cur.c[k];
-      // the next read's inputs in flight from here on
-      const uint64_t rest = em & (em - 1);
-      if (rest) pre((uint32_t)__builtin_ctzll(rest), cur);
-      wave_sync();
-      // ---- records: the two prefetched chunks, then the rest two chunks at a time ----
-      const uint64_t qa = rk0 & ~3ull;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) apply4(c[k], qa + (uint64_t)k * 4 * WAVE + 4 * lane, rk0, rk1, sh);
-      for (uint64_t q0 = qa + 2 * RCH; q0 < rk1; q0 += 2 * RCH) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const uint64_t q = q0 + (uint64_t)k * 4 * WAVE + 4 * lane;
-          c[k] = q < rk1 ? *(const u32x4 *)(L.rec_g + q) : u32x4{~0u, ~0u, ~0u, ~0u};
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) apply4(c[k], q0 + (uint64_t)k * 4 * WAVE + 4 * lane, rk0, rk1, sh);
-      }
-      wave_sync();
-      // ---- survivors in group order: lane w owns alive word w; listed in rounds of RLIST ----
-      const uint32_t nwd = (G + 31) / 32;
-      const uint32_t aw = lane < nwd ? (s.born[lane] & ~s.killed[lane]) : 0u;
-      const uint32_t cnt = (uint32_t)__popc(aw);
-      const uint32_t inc = wave_incl_scan_u32(cnt, lane);
-      const uint32_t ns = (uint32_t)__shfl((int)inc, 63, WAVE);
-      const uint64_t ooff = uniform_u64(s.slot[j].ooff);
-      const uint32_t ocap = uniform_u32(s.slot[j].ocap);
-      const uint32_t nput = ns < ocap ? ns : ocap;
-      for (uint32_t base = 0; base < nput; base += RLIST) {
-        uint32_t o = inc - cnt;
-        for (uint32_t bits = aw; bits; bits &= bits - 1, ++o)
-          if (o >= base && o < base + RLIST) s.list[o - base] = (uint16_t)(lane * 32 + __builtin_ctz(bits));
-        wave_sync();
-        const uint32_t end = nput - base < RLIST ? nput - base : RLIST;
-        for (uint32_t j0 = 0; j0 < end; j0 += 2 * WAVE) {
-          const uint32_t j1 = j0 + lane, j2 = j1 + WAVE;
-          u64x2 p1 = {0, 0}, p2 = {0, 0};
-          // a survivor's pair through its birth record (prec: births close together in op
-          // order) rather than its group slot (grp: one group run apart in output order)
-          if (j1 < end) p1 = *(const u64x2 *)(pairs + 2 * (rk0 + (L.prec ? s.bri[s.list[j1]] : s.list[j1])));
-          if (j2 < end) p2 = *(const u64x2 *)(pairs + 2 * (rk0 + (L.prec ? s.bri[s.list[j2]] : s.list[j2])));
-          if (j1 < end) R.value.set_a[ooff + base + j1] = p1.x, R.value.set_b[ooff + base + j1] = p1.y;
-          if (j2 < end) R.value.set_a[ooff + base + j2] = p2.x, R.value.set_b[ooff + base + j2] = p2.y;
-        }
-        wave_sync();
-      }
-      if (lane == j) setlen = ns, cap_err = ns > ocap;
-      wave_sync();
-    }
-    // ---- the batch's outputs (lane j: read b0 + j): set_len, or the capacity status ----
-    if (ok) {
-      const uint64_t r = s.slot[lane].r;
-      if (cap_err) R.status[r] = AM_ERR_CAPACITY;
-      else R.value.set_len[r] = setlen;
-    }
-    wave_sync();  // the slots are rewritten by the next batch
-  }
-}
-
-// ---------------------------------------------------------------- split fresh read, pass 2 by spans
-// k_grp_spans: k_grp_recs over the group-span view (include/antidote_mat.h key_nspan / gspan /
-// gsrc) -- one word per BORN group (birth op | kill op << 16) instead of one record per birth and
-// kill slot.  A fresh read has no base, so a group is alive iff its birth op is included and its
-// one effective kill (if any) is not; only an alive group reads its gsrc word (group | birth
-// record << 16) and sets its LDS bit: one atomicOr per survivor.  The batch structure, the
-// survivor listing and the pair gather are k_grp_recs's, and so are the outputs, bit for bit.
-// A read of a key without spans (AM_NSPAN_NONE: a group with two effective kills, ...) streams
-// the key's records here instead, k_grp_recs's born / killed rule without its prefetch: such
-// keys are rare (concurrent removes of one token), and a second launch for them, or a list of
-// them, costs every batch more than they do.
-constexpr int SPRE = 4;  // prefetched 16-byte span loads per lane: the first 1024 spans of a read
-struct SSlot {
-  uint64_t off0, rk0, ooff;
-  uint32_t r, nops, nb, G, ocap, nrec;  // nb == AM_NSPAN_NONE: by the nrec records
-};
-struct SSmem {
-  uint32_t alive[VG / 32], killed[VG / 32];  // (killed: the reads by records only)
-  uint32_t incl[VWORDS];
-  uint16_t list[RLIST];
-  uint16_t bri[VG];  // per alive group: its birth record (from the read's rk0)
-  SSlot slot[IWB];
-};
-struct SPre {  // a read's prefetched inputs: one bitmap word and SPRE span loads per lane
-  uint32_t w;
-  u32x4 c[SPRE];
-};
-
-template <int DMAX, int TYPE>
-__global__ void __launch_bounds__(BLOCK, 5) k_grp_spans(am_op_log L, am_read_batch B, am_read_result R, am_sel S,
-                                                        uint32_t short_opl, const uint32_t *ibm) {
-  __shared__ SSmem smem[NW];
-  SSmem &s = smem[threadIdx.x >> 6];
-  const uint32_t lane = threadIdx.x & (WAVE - 1);
-  const uint32_t sel0 = S.idx ? uniform_u32(S.range[0]) : 0u;
-  const uint64_t nsel = S.idx ? (uint64_t)(uniform_u32(S.range[1]) - sel0) : B.n_reads;
-  const uint64_t W = (uint64_t)gridDim.x * NW;
-  const uint64_t gw = (uint64_t)blockIdx.x * NW + uniform_u32(threadIdx.x >> 6);
-  const uint64_t *const pairs = L.prec ? L.prec : L.grp;
-  constexpr uint32_t SCH = (uint32_t)SPRE * 4 * WAVE;  // spans per pass of the wave
-
-  // spans [q0, q0 + SCH) of a read whose spans are [rk0, rk1) (lane i: four consecutive words per
-  // load, q0 a multiple of 4)
-  auto ld_spans = [&](uint64_t q0, uint64_t rk1, u32x4 (&c)[SPRE]) {
-#pragma unroll
-    for (int k = 0; k < SPRE; ++k) {
-      const uint64_t q = q0 + (uint64_t)k * 4 * WAVE + 4 * lane;
-      c[k] = q < rk1 ? *(const u32x4 *)(L.gspan + q) : u32x4{0, 0, 0, 0};
-    }
-  };
-  // prefetch read j of the slot table: bitmap words [t0 / 32, ...) (lane i: word i, the first
-  // 64), spans [rk0 & ~3, + SCH)
-  auto pre = [&](uint32_t j, SPre &p) {
-    const uint64_t off0 = s.slot[j].off0, rk0 = s.slot[j].rk0;
-    const uint32_t nops = s.slot[j].nops, nb = s.slot[j].nb;
-    const uint64_t t0 = off0 & ~31ull;
-    const uint32_t nw = (uint32_t)((off0 + nops - t0 + 31) / 32);
-    p.w = lane < nw ? ibm[(t0 >> 5) + lane] : 0u;
-    ld_spans(rk0 & ~3ull, rk0 + (nb == AM_NSPAN_NONE ? 0u : nb), p.c);
-  };
-  // one pass of spans against the LDS bitmap (bit = op + sh): the alive ones' gsrc words are
-  // loaded together (independent loads, one wait), then their bits and birth records set
-  auto apply = [&](const u32x4 (&c)[SPRE], uint64_t q0, uint64_t rk0, uint64_t rk1, uint32_t sh) {
-    uint32_t src[SPRE * 4];
-    uint32_t am = 0;
-#pragma unroll
-    for (int k = 0; k < SPRE; ++k) {
-      const uint64_t q = q0 + (uint64_t)k * 4 * WAVE + 4 * lane;
-      const uint32_t xs[4] = {c[k].x, c[k].y, c[k].z, c[k].w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bool inr = q + e >= rk0 && q + e < rk1;  // (a word of a neighbouring key is not looked at)
-        const uint32_t x = inr ? xs[e] : 0u;
-        const uint32_t b = (x & 0xFFFFu) + sh, kl = (x >> 16) + sh;
-        const bool inb = (s.incl[b >> 5] >> (b & 31)) & 1u, ink = (s.incl[kl >> 5] >> (kl & 31)) & 1u;
-        const bool al = inr && inb && (kl == b || !ink);
-        src[4 * k + e] = al ? L.gsrc[q + e] : 0u;
-        am |= (uint32_t)al << (4 * k + e);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < SPRE * 4; ++i)
-      if ((am >> i) & 1u) {
-        const uint32_t g = src[i] & 0xFFFFu;
-        atomicOr(s.alive + (g >> 5), 1u << (g & 31));
-        s.bri[g] = (uint16_t)(src[i] >> 16);  // a group's one birth
-      }
-  };
-
-  for (uint64_t b0 = gw * IWB; b0 < nsel; b0 += (uint64_t)IWB * W) {
-    // ---- lane j < IWB: read b0 + j -> slot j (the reads k_grp_incl took and left ok) ----
-    const uint64_t ii = b0 + lane;
-    bool ok = false;
-    if (lane < IWB && ii < nsel) {
-      GMeta mm;
-      read_meta(L, B, S.idx ? (uint64_t)S.idx[sel0 + ii] : ii, TYPE, mm);
-      ok = mm.st == AM_OK && wave_takes(L, B, mm, short_opl) && R.status[mm.r] == AM_OK;
-      if (ok) {
-        const uint32_t nb = L.key_nspan[mm.key];
-        SSlot &w = s.slot[lane];
-        const uint64_t o0 = R.value.set_off[mm.r], o1 = R.value.set_off[mm.r + 1];
-        w.off0 = mm.off0, w.rk0 = mm.rk0, w.ooff = o0;
-        w.r = (uint32_t)mm.r, w.nops = (uint32_t)(mm.off1 - mm.off0), w.nrec = (uint32_t)(mm.rk1 - mm.rk0);
-        // (a count beyond the key's record slots is no span view)
-        w.nb = nb > w.nrec ? AM_NSPAN_NONE : nb;
-        w.G = mm.G, w.ocap = o1 - o0 < 0xFFFFFFFFull ? (uint32_t)(o1 - o0) : 0xFFFFFFFFu;
-      }
-    }
-    uint64_t em = __ballot(ok);
-    wave_sync();
-    SPre cur;
-    if (em) pre((uint32_t)__builtin_ctzll(em), cur);
-    uint32_t setlen = 0;  // lane j: read j's survivor count
-    int32_t cap_err = 0;  // lane j: read j overflowed its capacity
-    for (; em; em &= em - 1) {
-      const uint32_t j = (uint32_t)__builtin_ctzll(em);
-      const uint64_t off0 = uniform_u64(s.slot[j].off0), rk0 = uniform_u64(s.slot[j].rk0);
-      const uint32_t nbj = uniform_u32(s.slot[j].nb);
-      const bool byrec = nbj == AM_NSPAN_NONE;
-      const uint64_t off1 = off0 + uniform_u32(s.slot[j].nops), rk1 = rk0 + (byrec ? 0u : nbj);
-      const uint32_t G = uniform_u32(s.slot[j].G);
-      const uint64_t t0 = off0 & ~31ull;
-      const uint32_t sh = (uint32_t)(off0 - t0), nw = (uint32_t)((off1 - t0 + 31) / 32);
-      // this read's bitmap into LDS (words past the first 64 straight from memory: long logs)
-      if (lane < nw) s.incl[lane] = cur.w;
-      for (uint32_t i = WAVE + lane; i < nw; i += WAVE) s.incl[i] = ibm[(t0 >> 5) + i];
-      for (uint32_t g = lane; g < (G + 31) / 32; g += WAVE) s.alive[g] = 0, s.killed[g] = 0;
-      u32x4 c[SPRE];
-#pragma unroll
-      for (int k = 0; k < SPRE; ++k) c[k] = cur.c[k];
-      // the next read's inputs in flight from here on
-      const uint64_t rest = em & (em - 1);
-      if (rest) pre((uint32_t)__builtin_ctzll(rest), cur);
-      wave_sync();
-      // ---- spans: the prefetched pass, then the rest a pass at a time ----
-      const uint64_t qa = rk0 & ~3ull;
-      apply(c, qa, rk0, rk1, sh);
-      for (uint64_t q0 = qa + SCH; q0 < rk1; q0 += SCH) {
-        ld_spans(q0, rk1, c);
-        apply(c, q0, rk0, rk1, sh);
-      }
-      if (byrec) {  // rare: the key's records by k_grp_recs's rule, then alive = born and not killed
-        const uint32_t nrec = uniform_u32(s.slot[j].nrec);
-        for (uint32_t i = lane; i < nrec; i += WAVE)
-          rec_apply(L.rec_g[rk0 + i], i, sh, s.incl, s.alive, s.killed, s.bri);
-        wave_sync();
-        for (uint32_t g = lane; g < (G + 31) / 32; g += WAVE) s.alive[g] &= ~s.killed[g];
-      }
-      wave_sync();
-      // ---- survivors in group order: lane w owns alive word w; listed in rounds of RLIST ----
-      const uint32_t nwd = (G + 31) / 32;
-      const uint32_t aw = lane < nwd ? s.alive[lane] : 0u;
-      const uint32_t cnt = (uint32_t)__popc(aw);
-      const uint32_t inc = wave_incl_scan_u32(cnt, lane);
-      const uint32_t ns = (uint32_t)__shfl((int)inc, 63, WAVE);
-      const uint64_t ooff = uniform_u64(s.slot[j].ooff);
-      const uint32_t ocap = uniform_u32(s.slot[j].ocap);
-      const uint32_t nput = ns < ocap ? ns : ocap;
-      for (uint32_t base = 0; base < nput; base += RLIST) {
-        uint32_t o = inc - cnt;
-        for (uint32_t bits = aw; bits; bits &= bits - 1, ++o)
-          if (o >= base && o < base + RLIST) s.list[o - base] = (uint16_t)(lane * 32 + __builtin_ctz(bits));
-        wave_sync();
-        const uint32_t end = nput - base < RLIST ? nput - base : RLIST;
-        for (uint32_t j0 = 0; j0 < end; j0 += 2 * WAVE) {
-          const uint32_t j1 = j0 + lane, j2 = j1 + WAVE;
-          u64x2 p1 = {0, 0}, p2 = {0, 0};
-          // a survivor's pair through its birth record (prec), as in k_grp_recs
-          if (j1 < end) p1 = *(const u64x2 *)(pairs + 2 * (rk0 + (L.prec ? s.bri[s.list[j1]] : s.list[j1])));
-          if (j2 < end) p2 = *(const u64x2 *)(pairs + 2 * (rk0 + (L.prec ? s.bri[s.list[j2]] : s.list[j2])));
-          if (j1 < end) R.value.set_a[ooff + base + j1] = p1.x, R.value.set_b[ooff + base + j1] = p1.y;
-          if (j2 < end) R.value.set_a[ooff + base + j2] = p2.x, R.value.set_b[ooff + base + j2] = p2.y;
-        }
-        wave_sync();
-      }
-      if (lane == j) setlen = ns, cap_err = ns > ocap;
-      wave_sync();
-    }
-    // ---- the batch's outputs (lane j: read b0 + j): set_len, or the capacity status ----
-    if (ok) {
-      const uint64_t r = s.slot[lane].r;
-      if (cap_err) R.status[r] = AM_ERR_CAPACITY;
-      else R.value.set_len[r] = setlen;
-    }
-    wave_sync();  // the slots are rewritten by the next batch
-  }
-}
+}  // namespace amk_grp
+#include "am_group_split.h"  // the split fresh read: k_grp_incl, k_grp_recs / k_grp_spans, launch_split
+namespace amk_grp {
 
 // ---------------------------------------------------------------- 16-lane row per short read
 // A wave takes 64 reads at a time: lane i checks read i against the row limits (the others
@@ -2164,77 +1363,6 @@ __global__ void __launch_bounds__(BLOCK) k_grp_row(am_log_arg LA, am_read_batch 
 }
 
 // ---------------------------------------------------------------- launchers
-// the split fresh read: k_grp_incl (op stream -> inclusion bitmap + scalars), then the record /
-// survivor pass: k_grp_spans when the log has the group-span view (key_nspan, gspan and gsrc all
-// set; a caller that nulls one gets k_grp_recs), else k_grp_recs
-template <int D, int TYPE, bool EXACT>
-int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_read_result *R, am_sel S,
-                 am_retry next, uint32_t short_opl) {
-  const uint64_t stride = L->snap_stride ? L->snap_stride : L->n_ops;
-  void *ibm = nullptr;
-  if (int rc = am_ctx_scratch(ctx, AM_SCR_INCL, (stride / 32 + 4) * 4, &ibm)) return rc;
-  // the lag view when the log has it: 4 + 2 D bytes of commit vector per op instead of 4 D
-  const bool lag = L->lag_ct && L->lag && L->key_lag;
-  const bool spans = L->key_nspan && L->gspan && L->gsrc;
-  // per kernel: each grid is sized by its own (occ_i[LAG]: the two inclusion instantiations
-  // have their own launch bounds)
-  static int occ_i[2] = {0, 0}, occ_w = 0, occ_s = 0;
-  if (!occ_i[0]) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_i[0], k_grp_incl<D, TYPE, EXACT, false>, BLOCK, 0) !=
-            hipSuccess ||
-        occ_i[0] < 1)
-      occ_i[0] = 2;
-  }
-  if (lag && !occ_i[1]) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_i[1], k_grp_incl<D, TYPE, EXACT, true>, BLOCK, 0) !=
-            hipSuccess ||
-        occ_i[1] < 1)
-      occ_i[1] = 2;
-  }
-  int &occ_r = spans ? occ_s : occ_w;  // the record pass that runs
-  if (!occ_r) {
-    const hipError_t e = spans ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_r, k_grp_spans<D, TYPE>, BLOCK, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_r, k_grp_recs<D, TYPE>, BLOCK, 0);
-    if (e != hipSuccess || occ_r < 1) occ_r = 1;
-  }
-  const uint64_t want_i = (B->n_reads + NW * IWB - 1) / (NW * IWB), want_w = want_i;
-  const uint64_t cap_p = (uint64_t)ctx->n_cu * occ_i[0], cap_l = (uint64_t)ctx->n_cu * occ_i[1];
-  const uint64_t bp = want_i < cap_p ? want_i : cap_p;          // the packed instantiation's grid
-  const uint64_t bi = lag ? (want_i < cap_l ? want_i : cap_l) : bp;  // the first launch's
-  const uint64_t bw = want_w < (uint64_t)ctx->n_cu * occ_r ? want_w : (uint64_t)ctx->n_cu * occ_r;
-  if (bi == 0) return AM_OK;
-  // the escape-mark rows of the inclusion pass: 64 lanes x 8 bytes per read slot of every wave of
-  // the larger grid (the two launches run one after the other and share them); a store without
-  // escaped ops never touches them
-  void *escv = nullptr;
-  if (int rc = am_ctx_scratch(ctx, AM_SCR_ESCM, (bi > bp ? bi : bp) * NW * IWB * WAVE * sizeof(uint64_t), &escv))
-    return rc;
-  uint64_t *const escr = (uint64_t *)escv;
-  if (lag) {
-    // the reads of packed-routed keys leave the lag instantiation through a list; the packed
-    // instantiation takes exactly those (an empty list: its blocks return at once)
-    am_retry routed;
-    am_sel rsel;
-    if (int rc = am_route_list(ctx, B->n_reads, &routed, &rsel)) return rc;
-    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, true>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B, *R,
-                       S, next, routed, short_opl, (uint32_t *)ibm, escr);
-    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bp), dim3(BLOCK), 0, ctx->stream, *L, *B,
-                       *R, rsel, next, am_retry{}, short_opl, (uint32_t *)ibm, escr);
-  } else {
-    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bp), dim3(BLOCK), 0, ctx->stream, *L, *B,
-                       *R, S, next, am_retry{}, short_opl, (uint32_t *)ibm, escr);
-  }
-  if (spans) {
-    hipLaunchKernelGGL((k_grp_spans<D, TYPE>), dim3((unsigned)bw), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S,
-                       short_opl, (const uint32_t *)ibm);
-  } else {
-    hipLaunchKernelGGL((k_grp_recs<D, TYPE>), dim3((unsigned)bw), dim3(BLOCK), 0, ctx->stream, *L, *B, *R, S,
-                       short_opl, (const uint32_t *)ibm);
-  }
-  AM_HIP(hipGetLastError());
-  return AM_OK;
-}
-
 template <int D, int TYPE, bool GENERAL, bool PACKED, bool EXACT>
 int launch_d(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_read_result *R, am_sel S, am_retry next,
              int tier) {
@@ -2245,15 +1373,11 @@ int launch_d(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_read_re
       if (!L->zone_vc && !ctx->tee_a) return launch_split<D, TYPE, EXACT>(ctx, L, B, R, S, next, short_opl);
     }
     static int occ = 0;
-    if (!occ) {
+    if (!occ)
       AM_HIP(hipFuncSetAttribute((const void *)k_grp_wave<D, TYPE, GENERAL, PACKED, EXACT>,
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_grp_wave<D, TYPE, GENERAL, PACKED, EXACT>, BLOCK,
-                                                       smem) != hipSuccess || occ < 1)
-        occ = 1;
-    }
-    uint64_t blocks = (B->n_reads + NW - 1) / NW, cap = (uint64_t)ctx->n_cu * occ;
-    if (blocks > cap) blocks = cap;
+    const uint64_t blocks =
+        grp_grid(ctx, occ, k_grp_wave<D, TYPE, GENERAL, PACKED, EXACT>, BLOCK, smem, 1, (B->n_reads + NW - 1) / NW);
     if (blocks == 0) return AM_OK;
     hipLaunchKernelGGL((k_grp_wave<D, TYPE, GENERAL, PACKED, EXACT>), dim3((unsigned)blocks), dim3(BLOCK), smem,
                        ctx->stream, *L, *B, *R, S, next, short_opl, GrpHint{ctx->grp_hint_in, ctx->tee_a, ctx->tee_b, ctx->tee_g, ctx->tee_shift,
@@ -2261,29 +1385,19 @@ int launch_d(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_read_re
                                                                   (unsigned long long *)ctx->stats});
   } else if (tier == AM_GRP_ROW) {
     static int occ = 0;
-    if (!occ) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_grp_row<D, TYPE, GENERAL, PACKED, EXACT>, BLOCK, 0) !=
-              hipSuccess || occ < 1)
-        occ = 2;
-    }
     const uint64_t waves = (B->n_reads + WAVE - 1) / WAVE;
-    uint64_t blocks = (waves + NW - 1) / NW, cap = (uint64_t)ctx->n_cu * occ;
-    if (blocks > cap) blocks = cap;
+    const uint64_t blocks =
+        grp_grid(ctx, occ, k_grp_row<D, TYPE, GENERAL, PACKED, EXACT>, BLOCK, 0, 2, (waves + NW - 1) / NW);
     if (blocks == 0) return AM_OK;
     hipLaunchKernelGGL((k_grp_row<D, TYPE, GENERAL, PACKED, EXACT>), dim3((unsigned)blocks), dim3(BLOCK), 0,
                        ctx->stream, *L, *B, *R, S, next);
   } else {
     constexpr size_t smem = sizeof(WgSmem<D>);
     static int occ = 0;
-    if (!occ) {
+    if (!occ)
       AM_HIP(hipFuncSetAttribute((const void *)k_grp_wg<D, TYPE, GENERAL, PACKED, EXACT>,
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_grp_wg<D, TYPE, GENERAL, PACKED, EXACT>, WBLOCK, smem) !=
-              hipSuccess || occ < 1)
-        occ = 1;
-    }
-    uint64_t blocks = B->n_reads, cap = (uint64_t)ctx->n_cu * occ;
-    if (blocks > cap) blocks = cap;
+    const uint64_t blocks = grp_grid(ctx, occ, k_grp_wg<D, TYPE, GENERAL, PACKED, EXACT>, WBLOCK, smem, 1, B->n_reads);
     if (blocks == 0) return AM_OK;
     hipLaunchKernelGGL((k_grp_wg<D, TYPE, GENERAL, PACKED, EXACT>), dim3((unsigned)blocks), dim3(WBLOCK), smem,
                        ctx->stream, *L, *B, *R, S, next);

@@ -1,5 +1,5 @@
 """The split fresh read's inclusion pass evaluates escaped ops after the loop over a wave batch's
-32 reads, not inside it (csrc/am_group.h k_grp_incl, the deferred phase): a read with escapes
+32 reads, not inside it (csrc/am_group_split.h k_grp_incl, the deferred phase): a read with escapes
 leaves its in-view partials in the batch's rows, its escape marks in a scratch row and its bit in
 a mask, and the later phase ORs the included escaped ops into the bitmap and merges their
 partials.  Hand-made keys put escapes where that can go wrong and the in-loop pass could not:

@@ -1,12 +1,13 @@
 """The group-span view (include/antidote_mat.h key_nspan / gspan / gsrc) and the span record pass of
-the split fresh read (csrc/am_group.h k_grp_spans).
+the split fresh read (csrc/am_group_split.h k_grp_spans; k_grp_recs shares its batch structure).
 
 1. The view from its definition: key_nspan, gspan and gsrc read back from the device and compared
    with a construction from the host log in Python (births in record order, effective kills, the
    output ranks taken from grp), on random logs and on the synthetic AW and MV logs.
 2. Reader cases on hand-made logs, each read three ways: through the spans, through rec_g (the same
    log with the span pointers nulled: every result column must be equal) and by the C oracle.
-3. Fallback: a key whose token two ops effectively kill has no spans and reads next to keys that do.
+3. Fallback: a key whose token two ops effectively kill has no spans and reads next to keys that do;
+   batch edges: such keys and capacity overflows at the first and last reads of the waves' batches.
 4. Apply: am_store_apply keeps a touched key's spans current, flips it to the sentinel on a second
    effective kill, and a GC prune leaves a readable key.
 Single-type batches on device stores, the batch clock, no zone index; every key is longer than the
@@ -212,8 +213,12 @@ def case_events(t=abi.AM_AWSET):
       NB = 1024: exactly the prefetched words, the second pass is AW's alone.
     - "kill_excluded" (and the fallback's "only the later kill included") needs a clock that is
       no prefix of the key's ops, which takes a second DC (clocks()): at D = 1 these keys read
-      under prefix clocks only, the split clock runs at D = 3 and D = 8."""
+      under prefix clocks only, the split clock runs at D = 3 and D = 8.
+    AW has one key more, "long_bitmap" (an MV key over 1024 ops leaves this tier, as above): 2180
+    ops, so its inclusion bitmap has more than 64 words -- the words past the prefetched 64 are
+    staged straight from memory -- with births in the first and in the last of them."""
     n_long = 1100 if t == abi.AM_AWSET else 1024
+    long_bitmap = {"long_bitmap": chain(40, 5) + nops(2100) + chain(40, 7, tok0=9000)} if t == abi.AM_AWSET else {}
     return {
         "no_groups": nops(70),
         "one_add": [("add", 1, 101, [])] + nops(66),
@@ -225,6 +230,7 @@ def case_events(t=abi.AM_AWSET):
         "nb255": chain(255, 40), "nb256": chain(256, 40), "nb257": chain(257, 40),
         "two_rounds": chain(300, 300),      # more than RLIST = 256 survivors
         "past_prefetch": chain(n_long, 900),  # AW: NB beyond the 1024 prefetched spans; 900 survive
+        **long_bitmap,
     }
 
 
@@ -295,19 +301,28 @@ def test_reader_cases(mat, t, n_dc):
         want = {"no_groups": 0, "one_add": 1, "same_op_kill": 1, "kill_before_birth": 1, "unborn_kill": 1,
                 "kill_excluded": 1, "nb255": 255, "nb256": 256, "nb257": 257, "two_rounds": 300,
                 "past_prefetch": 1100 if t == abi.AM_AWSET else 1024}
+        if "long_bitmap" in names:
+            want["long_bitmap"] = 80
         for n, nb in want.items():
             assert int(nspan[names.index(n)]) == nb, n
         # (the keys start at op slots 70, 137, 208, ...: most share bitmap words with their neighbours)
         ko = log.key_off.astype(np.int64)
         assert (ko[1:-1] % 32 != 0).sum() >= 10
-        for ci, clock in enumerate(clocks(keys, n_dc)):
+        cl = clocks(keys, n_dc)
+        split = cl[2] if n_dc > 1 else None
+        if "long_bitmap" in names:  # (it doubles the keys' time range: the prefix of the others' range too)
+            ko_l = ko[names.index("long_bitmap"):]
+            assert ko_l[1] - ko_l[0] == 2180 and (ko_l[1] - 1) // 32 - ko_l[0] // 32 >= 64
+            cl.append(clocks(keys[:names.index("long_bitmap")], n_dc)[1])
+        for ci, clock in enumerate(cl):
             a = three_ways(mat, dlog, log, keys, t, n_dc, clock, 1024)
             sl = dict(zip(names, a["set_len"].tolist()))
             if ci == 0:  # past every op
                 assert (sl["no_groups"], sl["one_add"], sl["same_op_kill"], sl["kill_before_birth"],
                         sl["unborn_kill"], sl["kill_excluded"]) == (0, 1, 1, 1, 1, 0)
                 assert sl["two_rounds"] == 300 and sl["past_prefetch"] == 900 and sl["nb257"] == 40
-            elif ci == 2:  # the kill op alone is out: the token lives
+                assert sl.get("long_bitmap", 12) == 12  # the first chain's 5 tokens and the last one's 7
+            elif clock is split:  # the kill op alone is out: the token lives
                 assert sl["kill_excluded"] == 1
         hi = clocks(keys, n_dc)[0]
         # capacity below the survivors: AM_ERR_CAPACITY for those reads, the others unchanged
@@ -368,6 +383,40 @@ def test_fallback_two_kills(mat, t, n_dc):
             assert (a["status"] == 0).all()
             if ci != 1:  # past every op, and the split clock: the later kill is included, 3 of 4 elems left
                 assert a["set_len"][1] == 3 and a["set_len"][4] == 3
+    finally:
+        st.close()
+
+
+@pytest.mark.parametrize("t", TYPES)
+def test_batch_edges(mat, t):
+    """70 reads in one launch: the waves take 32, 32 and 6 of them.  Keys without spans sit at the
+    batches' edges (reads 0, 31, 32, 69) and keys with more survivors than the capacity next to
+    them (reads 1, 30, 32, 68): AM_ERR_CAPACITY for exactly those reads and every other read the
+    oracle's, in order and with the selection reversed.  Read 32 is both: a key without spans
+    whose survivors exceed the capacity."""
+    n_dc, cap = 3, 8
+    kills = [("rm", 0, [1036], "x"), ("nop",), ("rm", 0, [1036])] + nops(30)  # 1036: elem 0's newest token
+    twice, twice_big = chain(40, 4) + kills, chain(40, 12) + kills            # 3 and 11 survivors
+    fallback, over = (0, 31, 32, 69), (1, 30, 32, 68)
+    ev = [chain(66 + 7 * i % 65, 3 + i % 6) for i in range(70)]  # 66 - 130 ops, 3 - 8 survivors
+    for i in over:
+        ev[i] = chain(66 + 7 * i % 65, 20)
+    for i in fallback:
+        ev[i] = twice_big if i in over else twice
+    keys, log = hand_log(t, n_dc, ev)
+    st = mat.store(log)
+    try:
+        st.index(abi.AM_INDEX_NONE)
+        dlog = st.device_log()
+        nspan, _ = check_view(mat, dlog, log)
+        assert [i for i in range(70) if int(nspan[i]) == NONE] == list(fallback)
+        hi = clocks(keys, n_dc)[0]
+        fwd = three_ways(mat, dlog, log, keys, t, n_dc, hi, cap)
+        assert [i for i in range(70) if fwd["status"][i] == abi.AM_ERR_CAPACITY] == sorted(over)
+        assert all(fwd["status"][i] == 0 for i in range(70) if i not in over)
+        assert fwd["set_len"][0] == 3 and fwd["set_len"][31] == 3 and fwd["set_len"][69] == 3
+        rev = three_ways(mat, dlog, log, keys, t, n_dc, hi, cap, sel=list(range(69, -1, -1)))
+        assert rev["status"].tolist() == fwd["status"].tolist()[::-1] and rev["pairs"] == fwd["pairs"][::-1]
     finally:
         st.close()
 
