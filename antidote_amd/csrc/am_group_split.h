@@ -32,10 +32,26 @@ struct ISlot {
   uint64_t off0, K, idb, key;
   uint32_t r, nops;
 };
+constexpr int SEGT = 4;               // 256-op tiles per segment of the lag instantiation
+constexpr uint32_t SEGOPS = SEGT * 256;  // ops per segment, and the most entries of its window list
+// per-lane LastOpCt maxima, transposed for the reduction; the lag instantiation's window list (u16
+// op indices within the segment, newest first) lives in the same bytes -- the maxima are written
+// when the list is done -- next to the segment's staged bitmap words
+template <int DMAX, bool LAG>
+struct ISred {
+  uint32_t mx[DMAX][WAVE];
+};
 template <int DMAX>
-struct ISmem {
+struct ISred<DMAX, true> {
+  union {
+    uint32_t mx[DMAX][WAVE];
+    uint16_t list[SEGOPS];
+  };
+  uint32_t stage[SEGOPS / 32];
+};
+template <int DMAX, bool LAG>
+struct ISmem : ISred<DMAX, LAG> {
   ISlot slot[IWB];
-  uint32_t mx[DMAX][WAVE];      // one read's per-lane LastOpCt maxima, transposed for the reduction
   // the batch's partials, by read: the in-view values as the tile loop leaves them, then merged
   // with the escaped ops' (the deferred phase); the outputs are derived from them once, as the
   // batch leaves
@@ -72,36 +88,46 @@ __device__ __forceinline__ uint32_t incl_tile(const Ent &x, const PkRead<DMAX> &
   return ib;
 }
 
-// the same test for the ops of the lane that the commit word left undecided (bits of win, the
-// window of am_inclwin.h): ops outside win neither pass here nor touch the maxima
-template <int DMAX, int OPL, class Ent>
-__device__ __forceinline__ uint32_t incl_tile_w(const Ent &x, const PkRead<DMAX> &pk, uint32_t win,
-                                                uint32_t (&mx)[DMAX]) {
-  uint32_t ib = 0;
-#pragma unroll
-  for (int k = 0; k < OPL; ++k) {
-    bool in = (win >> k) & 1u;
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) in = in && x(k, d) <= pk.thr[d];
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) mx[d] = max(mx[d], in ? x(k, d) : 0u);
-    ib |= (uint32_t)in << k;
+// the per-lane maxima a wave left in smx (transposed, synced) -> lane l: DC (l & 7)'s maximum.
+// Lane 8 d + c takes DC d's entries of lanes 8 c .. 8 c + 7, then an 8-lane max.
+template <int DMAX>
+__device__ __forceinline__ uint32_t mx_reduce(const uint32_t (*smx)[WAVE], uint32_t lane) {
+  uint32_t m = 0;
+  {
+    const uint32_t d = lane >> 3, c = lane & 7u;
+    if (d < (uint32_t)DMAX) {
+      const u32x4 a0 = *(const u32x4 *)&smx[d][8 * c], a1 = *(const u32x4 *)&smx[d][8 * c + 4];
+      m = max(max(max(a0.x, a0.y), max(a0.z, a0.w)), max(max(a1.x, a1.y), max(a1.z, a1.w)));
+    }
+    // lanes ^ 1, ^ 2, then the other quad of the eight (row_half_mirror): no lane addresses,
+    // which the compiler would compute once per batch and hold across the tile loop
+    m = max(m, dpp32<0xB1>(m));
+    m = max(m, dpp32<0x4E>(m));
+    m = max(m, dpp32<0x141>(m));
   }
-  return ib;
+  // from lane 8 d (its address from the opaque lane number, for the same reason)
+  uint32_t ql = lane;
+  asm volatile("" : "+v"(ql));
+  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((ql & 7u) << 5), (int)m);
 }
 
 // LAG: the read streams the lag view (am_op_log.lag_ct / lag / key_lag, 4 + 2 D bytes per op)
 // and rebuilds each packed entry X[d] - K = lag_ct - key_lag[d] - lag[d] in u32 (exact: the entry
 // fits u32 for every op the view holds); else the packed view (4 D bytes per op)
 //
-// Waves per SIMD, by clock width D.  The pass is bound by the chain of dependent loads of a read
-// (lag bases and newest commit words, then each window tile's lag lines), which more waves
-// cover.  The per-read loop holds the tile loop and the reduction only: escaped ops are
-// evaluated after the batch's loop, where no tile state is live, and what the batch's set-up
+// The lag instantiation does not evaluate the window ops (am_inclwin.h) in the tile loop, densely
+// and per tile: a segment of four tiles is classified from its commit words alone, its window ops
+// are compacted into a per-wave LDS list and evaluated in rounds of 64, one op per lane (a 4-byte
+// and nd 2-byte gathers per op), their bits ORed into bitmap words staged in LDS.  A C3 read has
+// ~75 window ops among 1024: two rounds instead of two dense window tiles, and one dependent step
+// (commit words -> lags) instead of one per window tile.
+//
+// Waves per SIMD, by clock width D.  The per-read loop holds the segment loop only: escaped ops
+// are evaluated after the batch's loop, where no tile state is live, and what the batch's set-up
 // and outputs derive from the lane number is computed per batch (sl_, ol), so neither weighs on
-// the tile loop's registers.  LAG (two tiles of commit words, the lag words of one, the window
-// state): 95-96 VGPRs at D = 8, five waves without a vector spill.  Packed (the tile's D x 4
-// entries): 103 VGPRs at D = 8, four waves (fifteen spilled at five).
+// the loop's registers.  LAG (a segment's commit words, then a round's lags and the maxima):
+// five waves without a vector spill at D = 8 (at six, 80 VGPRs, it spills 9-12).  Packed (the
+// tile's D x 4 entries): 103 VGPRs at D = 8, four waves (fifteen spilled at five).
 #ifndef AM_INCL_WAVES
 #define AM_INCL_WAVES(D) 4
 #endif
@@ -116,8 +142,8 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
   constexpr int OPL = 4;
   constexpr uint64_t TILE = (uint64_t)WAVE * OPL;
   constexpr uint32_t LPW = 32 / OPL;
-  __shared__ ISmem<DMAX> smem[NW];
-  ISmem<DMAX> &sm = smem[threadIdx.x >> 6];
+  __shared__ ISmem<DMAX, LAG> smem[NW];
+  ISmem<DMAX, LAG> &sm = smem[threadIdx.x >> 6];
   ISlot *sl = sm.slot;
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint32_t nd = EXACT ? (uint32_t)DMAX : L.n_dc;
@@ -177,138 +203,233 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
       const uint64_t off0 = uniform_u64(sl[j].off0), off1 = off0 + uniform_u32(sl[j].nops);
       PkRead<DMAX> pk;
       pk_setup(u, nd, uniform_u64(sl[j].K), pk);
-      uint32_t mx[DMAX], lb[DMAX];  // lb: the key's lag bases (LAG)
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) mx[d] = 0;
+      uint32_t lb[DMAX];  // the key's lag bases (LAG)
       if (LAG) {
         const uint64_t key = uniform_u64(sl[j].key);
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) lb[d] = uniform_u32(d < (int)nd ? (uint32_t)L.key_lag[key * nd + d] : 0u);
       }
       uint32_t cnt = 0, minex = 0xFFFFFFFFu, anyc = 0, anyesc = 0;
+      uint32_t mxr = 0;  // (LAG) lane l: DC (l & 7)'s maximum over the segments so far
       uint64_t escm = 0;  // the lane's escaped ops: bit OPL * tile + k (the first 64 / OPL tiles)
       const uint64_t t0 = off0 & ~31ull;  // 32-op aligned: lane groups of LPW fill whole bitmap words
-      // one tile's inclusion bits -> partials, escape marks and the bitmap words
-      auto tile_out = [&](uint64_t t, uint64_t g, uint32_t ib, uint32_t esc, uint32_t cand) {
-        if (pk.never) ib = 0;
-        cnt += (uint32_t)__popc(ib);
-        anyc |= cand;
-        anyesc |= esc;
-        const uint64_t ti = (t - t0) / TILE;
-        if (esc) escm |= ti < 64 / OPL ? (uint64_t)esc << (OPL * ti) : ~0ull;  // ~0: walk the key
-        const uint32_t ex = cand & ~ib;
-        if (ex) minex = min(minex, (uint32_t)(g - t0) + (uint32_t)__builtin_ctz(ex));
-        uint32_t word = ib << (OPL * (lane % LPW));
-#pragma unroll
-        for (uint32_t xo = 1; xo < LPW; xo <<= 1) word |= (uint32_t)__shfl_xor((int)word, (int)xo);
-        const uint64_t w0 = g & ~31ull;  // this lane group's word: ops [w0, w0 + 32)
-        if (lane % LPW == 0 && w0 < off1) {
-          if (w0 >= off0 && w0 + 32 <= off1) {
-            ibm[w0 >> 5] = word;
-          } else {  // a word shared with a neighbouring key: only this read's bits change
-            const uint32_t lo = off0 > w0 ? (uint32_t)(off0 - w0) : 0u;
-            const uint32_t hi = off1 < w0 + 32 ? (uint32_t)(off1 - w0) : 32u;
-            const uint32_t mask = (hi >= 32 ? ~0u : ((1u << hi) - 1u)) & ~((1u << lo) - 1u);
-            atomicAnd(ibm + (w0 >> 5), ~mask);
-            atomicOr(ibm + (w0 >> 5), word & mask);
-          }
-        }
-      };
       if constexpr (LAG) {
-        static_assert(OPL == 4, "four u16 lags per 8-byte load");
+        static_assert(OPL == 4 && TILE == 256 && SEGOPS == SEGT * TILE, "list entries: tile, lane, op of four");
         // The commit word alone decides most ops (am_inclwin.h): only ops in the window
-        // in_lim <= c < out_lim load their lags.  Tiles are walked newest first, so the newest
-        // included ops raise cmax (and with it in_lim) before the older ones are met; the commit
-        // words of tile t - 1 are in flight while tile t is evaluated (two register sets, no
-        // copies between them).  A whole tile the limits decide takes a short path (tile_const).
+        // in_lim <= c < out_lim need their lags.  The read is cut into segments of SEGT tiles,
+        // walked newest first (a C3 read is one segment), and a segment goes in phases:
+        //  1. its commit words, all tiles in flight together; the bound without loads over the
+        //     whole segment; then every op's class -- sure-IN bits into the staged words, escape
+        //     marks and partials as the tile loop of the packed view leaves them;
+        //  2. its window ops appended to the wave's list, newest first;
+        //  3. the list in rounds, one op per lane: the op's commit word and nd u16 lags gathered,
+        //     its entries rebuilt and tested, its bit ORed into the staged word, its entries folded
+        //     into the lane's maxima.  Each round raises cmax from the lanes' maxima; the next
+        //     round's entries are classified again first and those now IN take no loads;
+        //  4. the staged words stored, the maxima reduced into mxr (lane d: DC d).
+        // An older segment starts from the cmax the newer ones reached.
         int64_t cinf = AM_IW_NOBOUND;
+        int32_t lbm = INT32_MAX;  // the smallest lag base: the rounds' bound in u32 above it
 #pragma unroll
         for (int d = 0; d < DMAX; ++d)
-          if (d < (int)nd) cinf = am_iw_fold(cinf, pk.thr[d], lb[d]);
+          if (d < (int)nd) cinf = am_iw_fold(cinf, pk.thr[d], lb[d]), lbm = min(lbm, (int32_t)lb[d]);
         am_inclwin iw;
         am_iw_init(&iw, cinf, pk.never);
         const uint32_t cin_lim = am_iw_lim(iw.cin), out_lim = am_iw_lim(iw.hi);
         uint32_t in_lim = am_iw_in_lim(&iw);
-        uint32_t cA[OPL], cB[OPL];
-        auto load = [&](uint64_t t, uint32_t (&c)[OPL]) {
-          const uint64_t g = t + (uint64_t)lane * OPL;
+        const uint32_t lo = (uint32_t)(off0 - t0), nops = (uint32_t)(off1 - off0);  // the read's ops: [lo, lo + nops) from t0
+        uint16_t *const list = sm.list;
+        uint32_t *const stage = sm.stage;
+        const uint32_t nt = (uint32_t)((off1 - 1 - t0) / TILE) + 1u;
+        for (uint32_t sg = (nt + SEGT - 1) / SEGT; sg-- > 0;) {
+          const uint64_t sb = t0 + (uint64_t)sg * SEGOPS;
+          const uint32_t sr = sg * SEGOPS;  // sb - t0
+          // ---- 1. commit words, the bound without loads, classes ----
+          uint32_t c[SEGT][OPL];
 #pragma unroll
-          for (int k = 0; k < OPL; ++k) c[k] = 0;
-          if (g < off1) ld_n32<OPL>(L.lag_ct + g, c);
-        };
-        // a whole tile of included ops below every maximum, or of excluded ops: no shuffles
-        auto tile_const = [&](uint64_t g, bool in) {
-          if (in) cnt += OPL;
-          else minex = min(minex, (uint32_t)(g - t0));
-          anyc |= (1u << OPL) - 1u;
-          if (lane % LPW == 0) ibm[g >> 5] = in ? ~0u : 0u;  // every word lies inside the read
-        };
-        auto eval = [&](uint64_t t, const uint32_t (&c)[OPL]) {
-          const uint64_t g = t + (uint64_t)lane * OPL;
-          const bool whole = t >= off0 && t + TILE <= off1;
-          if (whole) {
-            static_assert(OPL == 4, "min / max of four words");
-            const uint32_t ch = max(max(c[0], c[1]), max(c[2], c[3]));  // (AM_PK_ESC is the largest word)
-            if (!__ballot(ch >= in_lim)) return tile_const(g, true);
-            const uint32_t cl = min(min(c[0], c[1]), min(c[2], c[3]));
-            if (!__ballot(cl < out_lim || ch == AM_PK_ESC)) return tile_const(g, false);
-          }
-          uint32_t esc = 0, cand = 0, sure = 0;  // sure: 1 + the lane's largest c <= cin
+          for (int k = 0; k < SEGT; ++k) {
+            const uint64_t g = sb + (uint64_t)k * TILE + (uint64_t)lane * OPL;
 #pragma unroll
-          for (int k = 0; k < OPL; ++k) {
-            const bool e = c[k] == AM_PK_ESC;
-            const bool inr = whole || (g + k >= off0 && g + k < off1);
-            esc |= (uint32_t)(inr && e) << k;
-            cand |= (uint32_t)(inr && !e) << k;
-            if (inr && c[k] < cin_lim) sure = max(sure, c[k] + 1u);
+            for (int i = 0; i < OPL; ++i) c[k][i] = 0;
+            if (g < off1) ld_n32<OPL>(L.lag_ct + g, c[k]);
           }
-          // the bound without loads, before this tile's own ops are classified
           if (in_lim < cin_lim) {
+            uint32_t sure = 0;  // 1 + the lane's largest c <= cin (AM_PK_ESC lies above every cin_lim)
+#pragma unroll
+            for (int k = 0; k < SEGT; ++k)
+#pragma unroll
+              for (int i = 0; i < OPL; ++i) {
+                const uint32_t q = sr + (uint32_t)k * (uint32_t)TILE + lane * OPL + (uint32_t)i;
+                if (q - lo < nops && c[k][i] < cin_lim) sure = max(sure, c[k][i] + 1u);
+              }
             const uint32_t m = uniform_u32(wave_max_u32_v(sure));
             if (m) am_iw_raise(&iw, am_iw_cmax_sure(m - 1u)), in_lim = am_iw_in_lim(&iw);
           }
-          uint32_t ib = 0, win = 0;
-#pragma unroll
-          for (int k = 0; k < OPL; ++k) {
-            const int cl = am_iw_class32(c[k], in_lim, out_lim);
-            ib |= (uint32_t)(cl == AM_IW_IN) << k;
-            win |= (uint32_t)(cl == AM_IW_WINDOW) << k;
-          }
-          ib &= cand, win &= cand;
-          if (__ballot(win != 0)) {  // lanes with an op in the window: a predicated 8-byte load per DC
-            uint32_t lw[DMAX][2];
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) {
-              uint2 v = {0, 0};
-              if (d < (int)nd && win) v = *(const uint2 *)(L.lag + (uint64_t)d * stride + g);
-              lw[d][0] = v.x, lw[d][1] = v.y;
+          uint32_t nl = 0;  // list entries (wave-uniform)
+          auto classify = [&](const int k, const uint32_t (&ck)[OPL]) {
+            const uint64_t t = sb + (uint64_t)k * TILE;
+            if (t >= off1) return;
+            const uint32_t q = sr + (uint32_t)k * (uint32_t)TILE + lane * OPL;  // the lane's first op, from t0
+            uint32_t *const sw = stage + k * (int)(TILE / 32) + lane / LPW;
+            const bool whole = t >= off0 && t + TILE <= off1;
+            if (whole) {  // a whole tile of included ops below every maximum, or of excluded ops
+              const uint32_t ch = max(max(ck[0], ck[1]), max(ck[2], ck[3]));  // (AM_PK_ESC is the largest word)
+              const uint32_t cl = min(min(ck[0], ck[1]), min(ck[2], ck[3]));
+              const bool in = !__ballot(ch >= in_lim);
+              if (in || !__ballot(cl < out_lim || ch == AM_PK_ESC)) {
+                if (in) cnt += OPL;
+                else minex = min(minex, q);
+                anyc |= (1u << OPL) - 1u;
+                if (lane % LPW == 0) *sw = in ? ~0u : 0u;
+                return;
+              }
             }
-            // (pad DCs d >= nd: c - lb[d] with lb = 0 lies under the always-passing pad threshold)
-            const uint32_t iwb = incl_tile_w<DMAX, OPL>(lag_ent(c, lw, lb), pk, win, mx);
-            ib |= iwb;
-            if (__ballot(iwb != 0)) {  // any lane's maxima bound every lane's
-              int64_t v = AM_IW_NOBOUND;
+            uint32_t esc = 0, cand = 0, ib = 0, win = 0;
 #pragma unroll
-              for (int d = 0; d < DMAX; ++d)
-                if (d < (int)nd) v = am_iw_fold(v, mx[d], lb[d]);
-              constexpr int64_t BIAS = 1ll << 32;  // v >= INT32_MIN: unsigned order
-              am_iw_raise(&iw, (int64_t)uniform_u64(wave_max_u64_v((uint64_t)(v + BIAS))) - BIAS);
-              in_lim = am_iw_in_lim(&iw);
+            for (int i = 0; i < OPL; ++i) {
+              const bool inr = whole || q + (uint32_t)i - lo < nops;
+              const int cl = am_iw_class32(ck[i], in_lim, out_lim);
+              esc |= (uint32_t)(inr && cl == AM_IW_ESCAPED) << i;
+              cand |= (uint32_t)(inr && cl != AM_IW_ESCAPED) << i;
+              ib |= (uint32_t)(inr && cl == AM_IW_IN) << i;
+              win |= (uint32_t)(inr && cl == AM_IW_WINDOW) << i;
+            }
+            cnt += (uint32_t)__popc(ib);
+            anyc |= cand;
+            anyesc |= esc;
+            const uint32_t ti = q / (uint32_t)TILE;
+            if (esc) escm |= ti < 64 / OPL ? (uint64_t)esc << (OPL * ti) : ~0ull;  // ~0: walk the key
+            const uint32_t ex = cand & ~ib & ~win;  // excluded by the commit word
+            if (ex) minex = min(minex, q + (uint32_t)__builtin_ctz(ex));
+            uint32_t word = ib << (OPL * (lane % LPW));
+#pragma unroll
+            for (uint32_t xo = 1; xo < LPW; xo <<= 1) word |= (uint32_t)__shfl_xor((int)word, (int)xo);
+            if (lane % LPW == 0) *sw = word;
+            // ---- 2. the tile's window ops onto the list, in descending op order ----
+            if (__ballot(win != 0)) {
+              const uint32_t pc = (uint32_t)__popc(win);
+              const uint32_t inc = wave_incl_scan_u32(pc, lane);
+              const uint32_t tot = lane_u32(inc, WAVE - 1);
+              uint32_t pos = nl + tot - inc;
+#pragma unroll
+              for (int i = OPL - 1; i >= 0; --i)
+                if ((win >> i) & 1u) list[pos++] = (uint16_t)((uint32_t)k * (uint32_t)TILE + lane * OPL + (uint32_t)i);
+              nl += tot;
+            }
+          };
+#pragma unroll
+          for (int k = SEGT - 1; k >= 0; --k) classify(k, c[k]);
+          wave_sync();
+          // ---- 3. rounds ----
+          if (nl) {
+            uint32_t mx[DMAX];  // the lane's maxima over its included window ops of this segment
+#pragma unroll
+            for (int d = 0; d < DMAX; ++d) mx[d] = 0;
+            // (loads are not predicated: a lane without an entry reads the segment's first slot)
+            const uint32_t *const cseg = L.lag_ct + sb;
+            const uint16_t *const lseg = L.lag + sb;
+            uint32_t cn = cseg[lane < nl ? (uint32_t)list[lane] : 0u];  // the coming round's commit words
+            auto round = [&](const uint32_t r0, auto first) {
+              const uint32_t i = r0 + lane;
+              const bool v = i < nl;
+              const uint32_t e = v ? (uint32_t)list[min(i, SEGOPS - 1u)] : 0u;
+              const uint32_t cc = cn;
+              uint32_t nx = 0;
+              if (r0 + WAVE < nl) nx = cseg[i + WAVE < nl ? (uint32_t)list[min(i + WAVE, SEGOPS - 1u)] : 0u];
+              bool need = v, sin = false;  // the first round's entries were classified just now
+              if constexpr (!decltype(first)::value) {
+                const int cl = am_iw_class32(cc, in_lim, out_lim);
+                sin = v && cl == AM_IW_IN, need = v && cl == AM_IW_WINDOW;
+              }
+              bool in = false;
+              if (decltype(first)::value || __ballot(need)) {
+                uint32_t lg[DMAX];
+#pragma unroll
+                for (int d = 0; d < DMAX; ++d) lg[d] = d < (int)nd ? (uint32_t)(lseg + (uint64_t)d * stride)[e] : 0u;
+                // (pad DCs d >= nd: c - lb[d] with lb = 0 lies under the always-passing pad threshold)
+                in = need;
+#pragma unroll
+                for (int d = 0; d < DMAX; ++d) {
+                  lg[d] = cc - (lb[d] + lg[d]);
+                  in = in && lg[d] <= pk.thr[d];
+                }
+#pragma unroll
+                for (int d = 0; d < DMAX; ++d) mx[d] = max(mx[d], in ? lg[d] : 0u);
+              }
+              cn = nx;
+              const bool inc = in || sin;
+              if (inc) atomicOr(stage + (e >> 5), 1u << (e & 31u));
+              cnt += (uint32_t)inc;
+              if (v && !inc) minex = min(minex, sr + e);
+              if (__ballot(in)) {
+                // any lane's maxima bound every lane's: min_d (mx[d] + lb[d]), in u32 above the
+                // smallest base (a saturated sum is a smaller bound, which is safe)
+                uint32_t f = 0xFFFFFFFFu;
+#pragma unroll
+                for (int d = 0; d < DMAX; ++d)
+                  if (d < (int)nd) f = am_iw_fold32(f, mx[d], lb[d], lbm);
+                am_iw_raise(&iw, am_iw_cmax_of32(uniform_u32(wave_max_u32_v(f)), lbm));
+                in_lim = am_iw_in_lim(&iw);
+              }
+            };
+            round(0u, std::true_type{});
+            for (uint32_t r0 = WAVE; r0 < nl; r0 += WAVE) round(r0, std::false_type{});
+            wave_sync();  // the list is done: its bytes take the maxima
+#pragma unroll
+            for (int d = 0; d < DMAX; ++d) sm.mx[d][lane] = mx[d];
+          }
+          // ---- 4. the staged words out (lane w: ops [sb + 32 w, + 32)) ----
+          {
+            uint32_t wl = lane;  // (opaque, as sl_ above)
+            asm volatile("" : "+v"(wl));
+            const uint64_t w0 = sb + 32ull * wl;
+            if (wl < SEGOPS / 32 && w0 < off1) {
+              const uint32_t word = stage[wl];
+              if (w0 >= off0 && w0 + 32 <= off1) {
+                ibm[w0 >> 5] = word;
+              } else {  // a word shared with a neighbouring key: only this read's bits change
+                const uint32_t blo = off0 > w0 ? (uint32_t)(off0 - w0) : 0u;
+                const uint32_t bhi = off1 < w0 + 32 ? (uint32_t)(off1 - w0) : 32u;
+                const uint32_t mask = (bhi >= 32 ? ~0u : ((1u << bhi) - 1u)) & ~((1u << blo) - 1u);
+                atomicAnd(ibm + (w0 >> 5), ~mask);
+                atomicOr(ibm + (w0 >> 5), word & mask);
+              }
             }
           }
-          tile_out(t, g, ib, esc, cand);
-        };
-        const uint64_t tl = t0 + (off1 - 1 - t0) / TILE * TILE;  // the last tile
-        load(tl, cA);
-        for (uint64_t t = tl;; t -= 2 * TILE) {
-          if (t > t0) load(t - TILE, cB);
-          eval(t, cA);
-          if (t == t0) break;
-          if (t - TILE > t0) load(t - 2 * TILE, cA);
-          eval(t - TILE, cB);
-          if (t - TILE == t0) break;
+          wave_sync();
+          if (nl) mxr = max(mxr, mx_reduce<DMAX>(sm.mx, lane));
+          wave_sync();  // list, staged words and maxima are rewritten by the next segment
         }
       } else {
+        uint32_t mx[DMAX];  // the lane's LastOpCt maxima
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) mx[d] = 0;
+        // one tile's inclusion bits -> partials, escape marks and the bitmap words
+        auto tile_out = [&](uint64_t t, uint64_t g, uint32_t ib, uint32_t esc, uint32_t cand) {
+          if (pk.never) ib = 0;
+          cnt += (uint32_t)__popc(ib);
+          anyc |= cand;
+          anyesc |= esc;
+          const uint64_t ti = (t - t0) / TILE;
+          if (esc) escm |= ti < 64 / OPL ? (uint64_t)esc << (OPL * ti) : ~0ull;  // ~0: walk the key
+          const uint32_t ex = cand & ~ib;
+          if (ex) minex = min(minex, (uint32_t)(g - t0) + (uint32_t)__builtin_ctz(ex));
+          uint32_t word = ib << (OPL * (lane % LPW));
+  #pragma unroll
+          for (uint32_t xo = 1; xo < LPW; xo <<= 1) word |= (uint32_t)__shfl_xor((int)word, (int)xo);
+          const uint64_t w0 = g & ~31ull;  // this lane group's word: ops [w0, w0 + 32)
+          if (lane % LPW == 0 && w0 < off1) {
+            if (w0 >= off0 && w0 + 32 <= off1) {
+              ibm[w0 >> 5] = word;
+            } else {  // a word shared with a neighbouring key: only this read's bits change
+              const uint32_t lo = off0 > w0 ? (uint32_t)(off0 - w0) : 0u;
+              const uint32_t hi = off1 < w0 + 32 ? (uint32_t)(off1 - w0) : 32u;
+              const uint32_t mask = (hi >= 32 ? ~0u : ((1u << hi) - 1u)) & ~((1u << lo) - 1u);
+              atomicAnd(ibm + (w0 >> 5), ~mask);
+              atomicOr(ibm + (w0 >> 5), word & mask);
+            }
+          }
+        };
         for (uint64_t t = t0; t < off1; t += TILE) {
           const uint64_t g = t + (uint64_t)lane * OPL;
           uint32_t esc = 0, cand = 0;
@@ -325,34 +446,20 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
                                     : incl_tile<DMAX, OPL, true>(pk_ent(x), pk, g, off0, off1, mx, esc, cand);
           tile_out(t, g, ib, esc, cand);
         }
-      }
-      // ---- the read's scalar outputs: LastOpCt maxima reduced through LDS (lane 8 d + c takes
-      //      DC d's entries of lanes 8 c .. 8 c + 7, then an 8-lane max), the rest by DPP ----
 #pragma unroll
-      for (int d = 0; d < DMAX; ++d) sm.mx[d][lane] = mx[d];
+        for (int d = 0; d < DMAX; ++d) sm.mx[d][lane] = mx[d];  // for the reduction below
+      }
+      // ---- the read's scalar outputs: LastOpCt maxima reduced through LDS (mx_reduce; the lag
+      //      instantiation's are reduced already, per segment), the rest by DPP ----
       const uint32_t count_p = wave_sum_u32_v(cnt);
       minex = wave_min_u32_v(minex);
       const bool cands = __ballot(anyc != 0) != 0;
       const bool escs = __ballot(anyesc != 0) != 0;
-      wave_sync();
-      uint32_t m = 0;
-      {
-        const uint32_t d = lane >> 3, c = lane & 7u;
-        if (d < (uint32_t)DMAX) {
-          const u32x4 a0 = *(const u32x4 *)&sm.mx[d][8 * c], a1 = *(const u32x4 *)&sm.mx[d][8 * c + 4];
-          m = max(max(max(a0.x, a0.y), max(a0.z, a0.w)), max(max(a1.x, a1.y), max(a1.z, a1.w)));
-        }
-        // lanes ^ 1, ^ 2, then the other quad of the eight (row_half_mirror): no lane addresses,
-        // which the compiler would compute once per batch and hold across the tile loop
-        m = max(m, dpp32<0xB1>(m));
-        m = max(m, dpp32<0x4E>(m));
-        m = max(m, dpp32<0x141>(m));
+      uint32_t mxd = mxr;
+      if constexpr (!LAG) {
+        wave_sync();
+        mxd = mx_reduce<DMAX>(sm.mx, lane);
       }
-      // lane d: DC d's packed maximum (relative to K), from lane 8 d (its address from the opaque
-      // lane number, for the same reason)
-      uint32_t ql = lane;
-      asm volatile("" : "+v"(ql));
-      const uint32_t mxd = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((ql & 7u) << 5), (int)m);
       // the read's in-view partials into the batch's LDS rows (slot j).  Ops outside the streamed
       // view (rare) are not evaluated here: the read leaves its lanes' escape marks in the wave's
       // scratch row j and its bit in escmask, and the deferred phase below merges them in

@@ -62,6 +62,20 @@ AM_IW_HD int64_t am_iw_cmax_of(const uint32_t *m, const uint32_t *lb, uint32_t n
 AM_IW_HD int64_t am_iw_cmax_sure(uint32_t c) { return (int64_t)c - AM_IW_LAG_MAX; }
 AM_IW_HD void am_iw_raise(am_inclwin *w, int64_t cmax) { w->cmax = cmax > w->cmax ? cmax : w->cmax; }
 
+/* The bound of running maxima in u32, for the rounds of the inclusion pass (one op per lane): one
+ * DC's term of min_d (m_d + lb_d) - lbm, lbm the smallest lag base of the DCs d < nd, saturating
+ * at 2^32 - 1 (a smaller bound is safe).  Start from 0xFFFFFFFF; the bound of the lanes' folds f is
+ * am_iw_cmax_of32(max over the lanes of f, lbm): any lane's maxima bound the read's. */
+AM_IW_HD uint32_t am_iw_fold32(uint32_t acc, uint32_t m, uint32_t lb, int32_t lbm) {
+#if defined(__HIPCC__)
+  const uint32_t t = __builtin_elementwise_add_sat(m, lb - (uint32_t)lbm);
+#else
+  const uint32_t s = m + (lb - (uint32_t)lbm), t = s < m ? 0xFFFFFFFFu : s;
+#endif
+  return t < acc ? t : acc;
+}
+AM_IW_HD int64_t am_iw_cmax_of32(uint32_t f, int32_t lbm) { return (int64_t)f + (int64_t)lbm; }
+
 AM_IW_HD int am_iw_sure_in(const am_inclwin *w, uint32_t c) { return c != AM_IW_ESC && (int64_t)c <= w->cin; }
 /* escape first: AM_PK_ESC lies above every hi */
 AM_IW_HD int am_iw_class(const am_inclwin *w, uint32_t c) {
