@@ -105,8 +105,10 @@ def make_log(rng, t, n_dc):
 _VIEW = {}
 
 
-def host_view(log):
-    """(commit times, per-key lag bases) of the host log, computed once."""
+def host_view(log, slot_off=None):
+    """(commit times, per-key lag bases, each key's first slot) of the host log, the first two
+    computed once.  slot_off: the store's slot offsets where its keys have room for appends
+    (a log ingested in place); by default the dense key_off, a store the log was just built into."""
     if id(log) not in _VIEW:
         n = log.n_ops
         ct = log.commit_time[:n].astype(np.int64)
@@ -114,27 +116,32 @@ def host_view(log):
         X = log.snap_vc[:, :n].astype(np.int64).copy()
         X[dc, np.arange(n)] = ct
         ko = log.key_off.astype(np.int64)
-        lbs = [(ct[ko[k]:ko[k + 1]][None, :] - X[:, ko[k]:ko[k + 1]]).min(axis=1) for k in range(log.n_keys)]
+        lbs = [(ct[ko[k]:ko[k + 1]][None, :] - X[:, ko[k]:ko[k + 1]]).min(axis=1) if ko[k + 1] > ko[k]
+               else np.zeros(log.n_dc, np.int64) for k in range(log.n_keys)]  # (a key pruned to empty)
         _VIEW[id(log)] = (log, ct, lbs)
-    return _VIEW[id(log)][1:]
+    first = log.key_off if slot_off is None else slot_off
+    return _VIEW[id(log)][1:] + (np.asarray(first).astype(np.int64),)
 
 
-def segment_lists(log, k, clock, pres=None):
+def segment_lists(log, k, clock, pres=None, slot_off=None):
     """Key k under the clock: per segment (1024 ops, 32-aligned from the key's start), newest first,
     the positions from the segment's start of its window ops when cmax comes from the bound without
     loads over that segment and the newer ones.  Escaped ops are not told apart here (the keys
-    the sizes are asserted on have none)."""
+    the sizes are asserted on have none).  slot_off: as host_view's -- the segments are cut from
+    the key's first slot in the store, not from its offset in the dense log."""
     nd = log.n_dc
-    ct, lbs = host_view(log)
+    ct, lbs, first = host_view(log, slot_off)
     a, b = int(log.key_off[k]), int(log.key_off[k + 1])
     lb = lbs[k]
     cin = min(int(clock[d]) + int(lb[d]) for d in range(nd))
     hi = cin + LAGMAX
     if pres is not None and pres != (1 << nd) - 1:
         cin, hi = -(1 << 62), -(1 << 62)
+    sh = int(first[k]) - a  # the key's ops lie at log position + sh in the store
+    a, b = a + sh, b + sh
     t0, cmax, out = a & ~31, -(1 << 62), []
     for s in range(t0 + (b - 1 - t0) // SEG * SEG, t0 - 1, -SEG):
-        lo, c = max(s, a), ct[max(s, a):min(s + SEG, b)]
+        lo, c = max(s, a), ct[max(s, a) - sh:min(s + SEG, b) - sh]
         sure = c[c <= cin]
         if len(sure):
             cmax = max(cmax, int(sure.max()) - LAGMAX)
@@ -142,11 +149,12 @@ def segment_lists(log, k, clock, pres=None):
     return out
 
 
-def steer(log, k, want):
-    """Clocks (one value for every DC) under which key k's list holds exactly the wanted sizes."""
+def steer(log, k, want, slot_off=None, seg=0):
+    """Clocks (one value for every DC) under which key k's list holds exactly the wanted sizes:
+    the list of its newest segment, or of its seg-th newest."""
     found = {}
     for x in range(T0 - 70_000, T0 + 140_000, 50):
-        n = len(segment_lists(log, k, [x] * log.n_dc)[0])
+        n = len(segment_lists(log, k, [x] * log.n_dc, None, slot_off)[seg])
         if n in want and n not in found:
             found[n] = x
     return found
