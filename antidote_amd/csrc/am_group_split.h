@@ -28,9 +28,25 @@ __device__ __forceinline__ uint32_t wave_min_u32_v(uint32_t v) {
   v = min(v, (uint32_t)__shfl_xor((int)v, 16, WAVE));
   return min(v, (uint32_t)__shfl_xor((int)v, 32, WAVE));
 }
-struct ISlot {
-  uint64_t off0, K, idb, key;
+// A read's slot: where its ops and outputs are, and its set-up (am_iw_read_setup, am_inclwin.h) --
+// the packed thresholds and, for the lag instantiation, the key's lag bases and the window's
+// limits -- computed by the batch's lane j for read j, 32 reads in one pass and their keys' lag
+// bases in one load latency, and read back wave-uniform when the wave comes to the read.
+constexpr uint32_t SLOT_NEVER = 1u, SLOT_MISS = 2u;  // fl: PkRead::never, PkRead::miss != 0
+struct ISlotHead {
+  uint64_t off0, K, idb;
   uint32_t r, nops;
+};
+template <int DMAX, bool LAG>
+struct alignas(16) ISlot : ISlotHead {
+  uint32_t thr[DMAX];
+  uint32_t fl;
+};
+template <int DMAX>
+struct alignas(16) ISlot<DMAX, true> : ISlotHead {
+  uint32_t thr[DMAX];
+  uint32_t lb[DMAX];
+  uint32_t lbm, cin_lim, out_lim, fl;  // (lbm: the int32 in u32)
 };
 constexpr int SEGT = 4;               // 256-op tiles per segment of the lag instantiation
 constexpr uint32_t SEGOPS = SEGT * 256;  // ops per segment, and the most entries of its window list
@@ -51,15 +67,19 @@ struct ISred<DMAX, true> {
 };
 template <int DMAX, bool LAG>
 struct ISmem : ISred<DMAX, LAG> {
-  ISlot slot[IWB];
+  ISlot<DMAX, LAG> slot[IWB];
   // the batch's partials, by read: the in-view values as the tile loop leaves them, then merged
   // with the escaped ops' (the deferred phase); the outputs are derived from them once, as the
   // batch leaves
-  uint64_t ct[DMAX][IWB];       // LastOpCt maxima, not yet masked by the presence
+  uint32_t ct[DMAX][IWB];       // the in-view LastOpCt maxima above the slot's K (u32, as the view's
+                                // entries; FLAG_INVIEW: any), not yet masked by the presence.  The
+                                // escaped ops' maxima are 64-bit and rare: they wait in the read's
+                                // scratch row (escr) and are merged as the columns are stored
   uint64_t mex[IWB];            // the first excluded op's slot (NONE: none)
   uint32_t count[IWB], pres[IWB];
-  uint32_t flags[IWB];          // with FLAG_BAD
+  uint32_t flags[IWB];          // with FLAG_BAD and FLAG_INVIEW
 };
+constexpr uint32_t FLAG_INVIEW = 0x200u;  // the read included an op of the streamed view: ct holds its maxima
 
 // ops [g, g + OPL) of the lane (OPL consecutive slots, g OPL-aligned), their entries x those of
 // the packed view (pk_ent) or rebuilt from the lag view where they are used (lag_ent, am_wave.h):
@@ -127,7 +147,8 @@ __device__ __forceinline__ uint32_t mx_reduce(const uint32_t (*smx)[WAVE], uint3
 // and outputs derive from the lane number is computed per batch (sl_, ol), so neither weighs on
 // the loop's registers.  LAG (a segment's commit words, then a round's lags and the maxima):
 // five waves without a vector spill at D = 8 (at six, 80 VGPRs, it spills 9-12).  Packed (the
-// tile's D x 4 entries): 103 VGPRs at D = 8, four waves (fifteen spilled at five).
+// tile's D x 4 entries): 97 VGPRs at D = 8, four waves.  A read's set-up (thresholds, lag bases,
+// window limits) is not in the loop either: the batch's lane j computes read j's into the slot.
 #ifndef AM_INCL_WAVES
 #define AM_INCL_WAVES(D) 4
 #endif
@@ -144,7 +165,7 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
   constexpr uint32_t LPW = 32 / OPL;
   __shared__ ISmem<DMAX, LAG> smem[NW];
   ISmem<DMAX, LAG> &sm = smem[threadIdx.x >> 6];
-  ISlot *sl = sm.slot;
+  ISlot<DMAX, LAG> *sl = sm.slot;
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint32_t nd = EXACT ? (uint32_t)DMAX : L.n_dc;
   const uint64_t stride = L.snap_stride ? L.snap_stride : L.n_ops;
@@ -153,8 +174,7 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
   const uint64_t W = (uint64_t)gridDim.x * NW;
   const uint64_t gw = (uint64_t)blockIdx.x * NW + uniform_u32(threadIdx.x >> 6);
   const uint64_t n = B.n_reads;
-  ReadU<DMAX> u;
-  read_inputs<DMAX, false, true>(L, nd, B, 0, u);  // one clock, no bases / TxIds
+  const uint32_t allmask = nd >= 32 ? 0xFFFFFFFFu : ((1u << nd) - 1u);
 
   for (uint64_t b0 = gw * IWB; b0 < nsel; b0 += (uint64_t)IWB * W) {
     // ---- lane j < IWB: read b0 + j -> slot j (errors and hand-offs leave here) ----
@@ -167,6 +187,10 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
     const uint64_t ii = b0 + sl_;
     bool elig = false, hand = false, route = false;
     uint64_t rr = 0;
+    // the batch's one clock (no bases / TxIds), read per batch: the reads' set-up below is its only
+    // use on this path, so it is not live across the reads' loops
+    ReadU<DMAX> u;
+    read_inputs<DMAX, false, true>(L, nd, B, 0, u);
     if (sl_ < IWB && ii < nsel) {
       GMeta mm;
       read_meta(L, B, S.idx ? (uint64_t)S.idx[sel0 + ii] : ii, TYPE, mm);
@@ -179,10 +203,26 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
         route = true;  // a packed-routed key: the packed instantiation's (launch_split)
       } else {
         elig = true;
-        ISlot &w = sl[sl_];
-        w.off0 = mm.off0, w.K = L.key_tbase[mm.key], w.idb = L.key_id_base ? L.key_id_base[mm.key] : 1;
-        w.key = mm.key;
+        // the read's set-up, one read per lane: the clock against this key's time base and lag bases
+        const uint64_t K = L.key_tbase[mm.key];
+        uint32_t lbk[DMAX], thr[DMAX];
+        if (LAG) {
+#pragma unroll
+          for (int d = 0; d < DMAX; ++d) lbk[d] = d < (int)nd ? (uint32_t)L.key_lag[mm.key * nd + d] : 0u;
+        }
+        am_iw_read rs;
+        am_iw_read_setup(u.S, u.spres, u.allmask, K, LAG ? lbk : nullptr, nd, (uint32_t)DMAX, thr, &rs);
+        ISlot<DMAX, LAG> &w = sl[sl_];
+        w.off0 = mm.off0, w.K = K, w.idb = L.key_id_base ? L.key_id_base[mm.key] : 1;
         w.r = (uint32_t)mm.r, w.nops = (uint32_t)(mm.off1 - mm.off0);
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) w.thr[d] = thr[d];
+        w.fl = (rs.never ? SLOT_NEVER : 0u) | (rs.miss ? SLOT_MISS : 0u);
+        if constexpr (LAG) {
+#pragma unroll
+          for (int d = 0; d < DMAX; ++d) w.lb[d] = lbk[d];
+          w.lbm = (uint32_t)rs.lbm, w.cin_lim = rs.cin_lim, w.out_lim = rs.out_lim;
+        }
       }
     }
     const uint64_t hm = __ballot(hand);
@@ -201,13 +241,17 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
     for (uint64_t em = emask; em; em &= em - 1) {
       const uint32_t j = (uint32_t)__builtin_ctzll(em);
       const uint64_t off0 = uniform_u64(sl[j].off0), off1 = off0 + uniform_u32(sl[j].nops);
+      // the read's set-up, from its slot (wave-uniform): no load from memory stands before the
+      // read's first commit words
       PkRead<DMAX> pk;
-      pk_setup(u, nd, uniform_u64(sl[j].K), pk);
-      uint32_t lb[DMAX];  // the key's lag bases (LAG)
-      if (LAG) {
-        const uint64_t key = uniform_u64(sl[j].key);
 #pragma unroll
-        for (int d = 0; d < DMAX; ++d) lb[d] = uniform_u32(d < (int)nd ? (uint32_t)L.key_lag[key * nd + d] : 0u);
+      for (int d = 0; d < DMAX; ++d) pk.thr[d] = uniform_u32(sl[j].thr[d]);
+      const uint32_t sfl = uniform_u32(sl[j].fl);
+      pk.never = (sfl & SLOT_NEVER) != 0;  // (the lag instantiation's is in its limits)
+      uint32_t lb[DMAX];  // the key's lag bases (LAG)
+      if constexpr (LAG) {
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) lb[d] = uniform_u32(sl[j].lb[d]);
       }
       uint32_t cnt = 0, minex = 0xFFFFFFFFu, anyc = 0, anyesc = 0;
       uint32_t mxr = 0;  // (LAG) lane l: DC (l & 7)'s maximum over the segments so far
@@ -228,15 +272,12 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
         //     round's entries are classified again first and those now IN take no loads;
         //  4. the staged words stored, the maxima reduced into mxr (lane d: DC d).
         // An older segment starts from the cmax the newer ones reached.
-        int64_t cinf = AM_IW_NOBOUND;
-        int32_t lbm = INT32_MAX;  // the smallest lag base: the rounds' bound in u32 above it
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d)
-          if (d < (int)nd) cinf = am_iw_fold(cinf, pk.thr[d], lb[d]), lbm = min(lbm, (int32_t)lb[d]);
-        am_inclwin iw;
-        am_iw_init(&iw, cinf, pk.never);
-        const uint32_t cin_lim = am_iw_lim(iw.cin), out_lim = am_iw_lim(iw.hi);
-        uint32_t in_lim = am_iw_in_lim(&iw);
+        // The window's state is u32 limits (am_inclwin.h): in_lim = min(cin_lim, cmax_lim), and
+        // since cin_lim is fixed the running bound is kept already capped -- cmax_lim starts at 0
+        // and a raise is a max, so min(cin_lim, max(in_lim, raise)) is the same value.
+        const int32_t lbm = (int32_t)uniform_u32(sl[j].lbm);  // the smallest lag base: the rounds' bound in u32 above it
+        const uint32_t cin_lim = uniform_u32(sl[j].cin_lim), out_lim = uniform_u32(sl[j].out_lim);
+        uint32_t in_lim = 0;
         const uint32_t lo = (uint32_t)(off0 - t0), nops = (uint32_t)(off1 - off0);  // the read's ops: [lo, lo + nops) from t0
         uint16_t *const list = sm.list;
         uint32_t *const stage = sm.stage;
@@ -263,7 +304,7 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
                 if (q - lo < nops && c[k][i] < cin_lim) sure = max(sure, c[k][i] + 1u);
               }
             const uint32_t m = uniform_u32(wave_max_u32_v(sure));
-            if (m) am_iw_raise(&iw, am_iw_cmax_sure(m - 1u)), in_lim = am_iw_in_lim(&iw);
+            if (m) in_lim = min(cin_lim, am_iw_lim_raise(in_lim, am_iw_lim_sure(m - 1u)));
           }
           uint32_t nl = 0;  // list entries (wave-uniform)
           auto classify = [&](const int k, const uint32_t (&ck)[OPL]) {
@@ -368,8 +409,7 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
 #pragma unroll
                 for (int d = 0; d < DMAX; ++d)
                   if (d < (int)nd) f = am_iw_fold32(f, mx[d], lb[d], lbm);
-                am_iw_raise(&iw, am_iw_cmax_of32(uniform_u32(wave_max_u32_v(f)), lbm));
-                in_lim = am_iw_in_lim(&iw);
+                in_lim = min(cin_lim, am_iw_lim_raise(in_lim, am_iw_lim_of32(uniform_u32(wave_max_u32_v(f)), lbm)));
               }
             };
             round(0u, std::true_type{});
@@ -463,11 +503,13 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
       // the read's in-view partials into the batch's LDS rows (slot j).  Ops outside the streamed
       // view (rare) are not evaluated here: the read leaves its lanes' escape marks in the wave's
       // scratch row j and its bit in escmask, and the deferred phase below merges them in
-      if (lane < nd) sm.ct[lane][j] = count_p ? pk.K + mxd : 0;
+      uint32_t cl_ = lane;  // (opaque, as sl_ above: the row's address is not held across the loops)
+      asm volatile("" : "+v"(cl_));
+      if (cl_ < nd) sm.ct[cl_][j] = mxd;
       if (lane == 0) {
-        sm.flags[j] = cands ? pk.miss : 0u;
+        sm.flags[j] = ((cands && (sfl & SLOT_MISS)) ? (uint32_t)AM_FLAG_MISSING_DC_LOGGED : 0u) | (count_p ? FLAG_INVIEW : 0u);
         sm.count[j] = count_p;
-        sm.pres[j] = count_p ? u.allmask : 0u;
+        sm.pres[j] = count_p ? allmask : 0u;
         sm.mex[j] = minex == 0xFFFFFFFFu ? NONE : t0 + minex;
       }
       if (escs) {
@@ -480,7 +522,10 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
     //      escape reader; the included ones' bits are ORed into the bitmap and their partials
     //      merged into the read's row.  No tile state is live here, so the D-wide u64 values of
     //      esc_load / eval_op do not weigh on the tile loop's registers ----
-    if (escmask) __builtin_amdgcn_s_waitcnt(0);  // the batch's bitmap words and mark rows are out
+    if (escmask) {
+      __builtin_amdgcn_s_waitcnt(0);  // the batch's bitmap words and mark rows are out
+      read_inputs<DMAX, false, true>(L, nd, B, 0, u);  // the clock again: not held across the reads' loops
+    }
     for (uint32_t xm = escmask; xm; xm &= xm - 1) {
       const uint32_t j = (uint32_t)__builtin_ctz(xm);
       const uint64_t off0 = uniform_u64(sl[j].off0), off1 = off0 + uniform_u32(sl[j].nops);
@@ -523,7 +568,9 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
         const uint64_t am = wave_max_u64_v(a.mx[d]);
         if ((uint32_t)d == lane) emx = am;
       }
-      if (lane < nd) sm.ct[lane][j] = umax64(sm.ct[lane][j], emx);
+      // the escaped ops' maxima are full-width (an escaped entry may lie below K, or 2^32 and more
+      // above it): they take the read's scratch row, whose marks are consumed, lane d: DC d
+      if (lane < nd) escw[(uint64_t)j * WAVE + lane] = emx;
       if (lane == 0) {
         sm.flags[j] |= eflags;
         sm.count[j] += ecount;
@@ -531,6 +578,7 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
         sm.mex[j] = umin64(sm.mex[j], emex);
       }
     }
+    if (escmask) __builtin_amdgcn_s_waitcnt(0);  // the escaped ops' maxima are out: another lane reads them
     wave_sync();
     // ---- the batch's outputs, derived from the merged partials: one coalesced store per column
     //      (lane j: read b0 + j) ----
@@ -551,9 +599,16 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
         R.last_ct_pres[r] = opres;
         R.is_new_ss[r] = c > 0;
         R.count[r] = c;
+        // the columns: the slot's K under the in-view maxima, and the escaped ops' merged in 64 bits
+        const uint64_t K = sl[ol].K;
+        const bool inview = (flags & FLAG_INVIEW) != 0, esc = ((escmask >> ol) & 1u) != 0;
 #pragma unroll
         for (int d = 0; d < DMAX; ++d)
-          if (d < (int)nd) R.last_ct[(uint64_t)d * n + r] = ((opres >> d) & 1u) ? sm.ct[d][ol] : 0;
+          if (d < (int)nd) {
+            uint64_t v = inview ? K + sm.ct[d][ol] : 0;
+            if (esc) v = umax64(v, escw[(uint64_t)ol * WAVE + d]);
+            R.last_ct[(uint64_t)d * n + r] = ((opres >> d) & 1u) ? v : 0;
+          }
       }
     }
     wave_sync();  // the slots are rewritten by the next batch

@@ -95,3 +95,65 @@ AM_IW_HD int am_iw_class32(uint32_t c, uint32_t in_lim, uint32_t out_lim) {
   if (c >= out_lim) return AM_IW_OUT;
   return c < in_lim ? AM_IW_IN : AM_IW_WINDOW;
 }
+/* The running bound as a limit.  am_iw_lim is monotone, so am_iw_in_lim(w) == min(cin_lim, cmax_lim)
+ * with cin_lim = am_iw_lim(cin) and cmax_lim = am_iw_lim(cmax): cmax_lim starts at 0 (cmax = -1) and
+ * a raise is a u32 max with the limit of the new bound, which the two kinds of raise give in 32 bits:
+ *   am_iw_lim_sure(c)      == am_iw_lim(am_iw_cmax_sure(c))       c <= 2^32 - 2 a sure-in commit word
+ *   am_iw_lim_of32(f, lbm) == am_iw_lim(am_iw_cmax_of32(f, lbm))  f the lanes' largest am_iw_fold32 */
+AM_IW_HD uint32_t am_iw_lim_sure(uint32_t c) { return c > 0xFFFEu ? c - 0xFFFEu : 0u; }
+AM_IW_HD uint32_t am_iw_lim_of32(uint32_t f, int32_t lbm) {
+  if (lbm >= 0) {
+    const uint32_t s = f + (uint32_t)lbm;
+    return (s < f || s >= 0xFFFFFFFEu) ? 0xFFFFFFFFu : s + 1u;
+  }
+  const uint32_t n = 0u - (uint32_t)lbm; /* |lbm|, 1 .. 2^31 */
+  return f < n ? 0u : f - n + 1u;
+}
+AM_IW_HD uint32_t am_iw_lim_raise(uint32_t cmax_lim, uint32_t lim) { return lim > cmax_lim ? lim : cmax_lim; }
+
+/* A read's set-up, from its clock and its key: what the inclusion pass needs of them before it meets
+ * an op.  The clock is S[d] for the DCs d < nd in spres (all the log's DCs: allmask); K the key's
+ * time base; lb the key's lag bases (null: the read streams the packed view, and only thr, never
+ * and miss are set).  thr[d], d < dmax: the packed thresholds (PkRead::thr: min(S_d - K, 2^32 - 2),
+ * 0 where S_d < K, AM_PK_ESC for the pad DCs d >= nd); never / miss as PkRead's. */
+typedef struct am_iw_read {
+  int never;        /* no op passes: a DC missing from the clock or below K */
+  int miss;         /* a DC of the ops is not in the clock */
+  int32_t lbm;      /* the smallest lag base of the DCs d < nd (am_iw_fold32) */
+  uint32_t cin_lim; /* am_iw_lim(cin) */
+  uint32_t out_lim; /* am_iw_lim(hi) */
+} am_iw_read;
+#if defined(__HIPCC__)
+#define AM_IW_UNROLL _Pragma("unroll")
+#else
+#define AM_IW_UNROLL
+#endif
+AM_IW_HD uint32_t am_iw_thr(uint64_t s, uint64_t K) {
+  return s < K ? 0u : (s - K >= (uint64_t)AM_IW_ESC ? AM_IW_ESC - 1u : (uint32_t)(s - K));
+}
+AM_IW_HD void am_iw_read_setup(const uint64_t *S, uint32_t spres, uint32_t allmask, uint64_t K, const uint32_t *lb,
+                               uint32_t nd, uint32_t dmax, uint32_t *thr, am_iw_read *o) {
+  int64_t f = 0; /* am_iw_fold over the DCs d < nd, from DC 0's term (no 64-bit start value to hold) */
+  int32_t lbm = INT32_MAX;
+  const int miss = (allmask & ~spres) != 0;
+  int never = miss;
+  AM_IW_UNROLL
+  for (uint32_t d = 0; d < dmax; ++d) {
+    if (d >= nd) {
+      thr[d] = AM_IW_ESC;
+      continue;
+    }
+    const uint64_t s = ((spres >> d) & 1u) ? S[d] : 0u;
+    never |= s < K;
+    thr[d] = am_iw_thr(s, K);
+    if (lb) {
+      const int64_t t = (int64_t)thr[d] + (int64_t)(int32_t)lb[d];
+      f = (d == 0 || t < f) ? t : f;
+      lbm = (int32_t)lb[d] < lbm ? (int32_t)lb[d] : lbm;
+    }
+  }
+  am_inclwin w;
+  am_iw_init(&w, (lb && nd) ? f : AM_IW_NOBOUND, never);
+  o->never = never, o->miss = miss, o->lbm = lbm;
+  o->cin_lim = am_iw_lim(w.cin), o->out_lim = am_iw_lim(w.hi);
+}
