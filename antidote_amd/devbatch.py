@@ -33,7 +33,9 @@ class DeviceReads:
         self.types = types if types is not None else torch.full((n_reads,), type_, dtype=torch.uint8, device=dev)
         present = set(int(x) for x in torch.unique(self.types).cpu().tolist()) if type_ == 0 else {type_}
         self.read_vc = _u64_tensor(list(clock), dev)
-        self.read_pres = torch.tensor([pres if pres is not None else (1 << n_dc) - 1], dtype=torch.int32, device=dev)
+        # (a u32 mask viewed as int32: bit 31 set at n_dc = AM_MAX_DC does not fit a signed literal)
+        mask = np.asarray([pres if pres is not None else (1 << n_dc) - 1], dtype=np.uint32)
+        self.read_pres = torch.from_numpy(mask.view(np.int32)).to(dev)
         self.base_ignore = None
         self.base_vc = self.base_pres = self.base_last_op = None
         self.base_v0 = self.base_v1 = self.base_vflag = None

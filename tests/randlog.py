@@ -75,10 +75,32 @@ def rand_key_ops(rng, t, n_dc, n_ops, partial=False, txids=False, bad_rate=0.0, 
     return ops
 
 
-def rand_clock(rng, n_dc, lo, hi, partial=False):
+FAR_DCS = (0, 16, 30, 31)
+
+
+def far_bc_effects(rng, n_dc, ops, rate=0.5):
+    """Rewrite about `rate` of a bounded counter's effects to increments, decrements and transfers
+    among the DCs 0, 16, 30, 31 (those the log has) and n_dc - 1: above 16 DCs these are P slots
+    past 16 * n_dc, and at 32 the last D slot n_dc * n_dc + 31.  Returns the ops."""
+    ends = sorted({d for d in FAR_DCS if d < n_dc} | {n_dc - 1})
+    for op in ops:
+        if op.type != abi.AM_BCOUNTER or op.bad or rng.random() >= rate:
+            continue
+        k = rng.choice(["increment", "decrement", "transfer", "transfer"])
+        if k == "transfer":
+            op.effect = (k, rng.randint(1, 50), rng.choice(ends), rng.choice(ends))
+        else:
+            op.effect = (k, rng.randint(1, 50), rng.choice(ends))
+    return ops
+
+
+def rand_clock(rng, n_dc, lo, hi, partial=False, miss=0.2):
+    """miss: the chance that a partial clock lacks a DC.  An op is excluded when its snapshot names
+    a DC the read clock lacks, so at many DCs the default leaves no read with an op; the wide
+    tests pass about 1 / n_dc."""
     c = {}
     for d in range(n_dc):
-        if partial and rng.random() < 0.2:
+        if partial and rng.random() < miss:
             continue
         c[d] = rng.randint(lo, hi)
     return c

@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 from antidote_amd import abi
-from antidote_amd.oplog import HostLog, Read
+from antidote_amd.oplog import HostBatch, HostLog, Read
+from oracle import amo
 from tests import randlog
 from tests.test_gpu_gc import _key_ops
 
@@ -43,11 +44,33 @@ def _reads_equal(mat, sa, sb, n_keys, types, n_dc, rng):
         assert ha.result(i) == hb.result(i), (i, ha.result(i), hb.result(i))
 
 
-@pytest.mark.parametrize("seed", range(4))
+def _oracle_reads(mat, st, n_keys, types, n_dc, rng):
+    """Reads of every key through the store against the oracle on the store's own downloaded log
+    (dense CSR, explicit op ids), and the view counters against the numpy count of that log; for
+    stores of more than 16 DCs."""
+    from tests.test_gpu_lagcadence import _DownLog, view_counts
+    mlog = _DownLog(st.download(), n_dc)
+    got, want = st.view_stats(), view_counts(mlog)[0]
+    assert n_dc > 16  # no lag view: nothing escapes it, nothing is routed
+    assert (got["ops"], got["pk_esc_ops"]) == (want["ops"], want["pk_esc_ops"]), (got, want)
+    assert got["lag_only_esc_ops"] == got["routed_keys"] == got["routed_ops"] == 0, got
+    assert not st.device_log().lag_ct
+    for lo in (0, 150):
+        reads = [Read(k, types[k], {d: rng.randint(lo, 400) for d in range(n_dc)}) for k in range(n_keys)]
+        caps = randlog.caps_for(reads, n_dc, 1024)
+        dev, ref = mat.read_batch(st, reads, caps), amo.materialize(mlog, HostBatch(n_dc, reads, caps))
+        for i in range(n_keys):
+            assert dev.result(i) == ref.result(i), (i, types[i], dev.result(i), ref.result(i))
+
+
+@pytest.mark.parametrize("seed", range(6))
 def test_gpu_apply_matches_rebuild(mat, seed):
+    """(seeds 4 and 5: 17 and 32 DCs -- k_upd_scatter<0> and the mx[AM_MAX_DC] paths of am_apply.hip /
+    am_pack.hip; there every round's reads are also compared with the oracle on the downloaded
+    log, and the view counters with their numpy count.)"""
     rng = random.Random(9300 + seed)
-    n_dc = [1, 3, 5, 8][seed]
-    partial = seed == 3
+    n_dc = [1, 3, 5, 8, 17, 32][seed]
+    partial = seed in (3, 5)
     n_keys = 64
     types = [randlog.TYPES[k % 5] for k in range(n_keys)]
     keys = [randlog.rand_key_ops(rng, types[k], n_dc, rng.choice([0, 1, 5, 20, 40]), partial=partial,
@@ -98,6 +121,8 @@ def test_gpu_apply_matches_rebuild(mat, seed):
                 nst.close()
             _same_store(inp.download(), ref.download(), n_keys)
             _reads_equal(mat, inp, ref, n_keys, full_types, n_dc, rng)
+            if n_dc > 16:
+                _oracle_reads(mat, inp, n_keys, full_types, n_dc, rng)
         assert applied_rounds >= 2, applied_rounds  # both paths taken: in place and (a key outgrew its room) rebuild
     finally:
         inp.close()
@@ -177,10 +202,20 @@ def test_gpu_vnode_inserts_in_place(mat):
     in-place path: after the first insert builds the room, batches touching few keys do not
     rebuild the store, and every key's tuple header, op ids and snapshot dict match the oracle's
     VnodeState."""
+    _vnode_inserts_in_place(mat, 3)
+
+
+def test_gpu_vnode_inserts_in_place_32_dcs(mat):
+    """The same history at 32 DCs (the draws do not depend on the width, so the same batches take
+    the in-place path): am_store_apply with mx[AM_MAX_DC] and commit DC 31."""
+    _vnode_inserts_in_place(mat, 32)
+
+
+def _vnode_inserts_in_place(mat, n_dc):
     from oracle import ref_materializer as R
     from tests.test_gpu_vnode import KeyGen, compare_state
     rng = random.Random(9500)
-    n_dc, n_keys = 3, 40
+    n_keys = 40
     types = [randlog.TYPES[k % 4] for k in range(n_keys)]
     gens = [KeyGen(rng, types[k], n_dc, 10 + rng.randint(0, 50)) for k in range(n_keys)]
     vn = mat.vnode(n_dc, n_keys)

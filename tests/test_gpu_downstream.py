@@ -228,7 +228,7 @@ def bc_values(n_dc, rng):
     return out
 
 
-@pytest.mark.parametrize("n_dc", [1, 3, 16])
+@pytest.mark.parametrize("n_dc", [1, 3, 16, 32])
 def test_gpu_downstream_bounded_counter(mat, n_dc):
     rng = random.Random(100 + n_dc)
     states = bc_values(n_dc, rng)

@@ -303,3 +303,14 @@ def test_eager_random_batch_is_accepted_by_the_oracle():
 @pytest.mark.gpu
 def test_gpu_eager_random_batch(mat):
     check(mat, 3, list(random_batch()))
+
+
+@pytest.mark.gpu
+def test_gpu_eager_random_batch_32_dcs(mat):
+    """The same batch shape at AM_MAX_DC: bounded counters are CLS_BIG from 11 DCs on (am_eager.hip),
+    their slots run to 32 * 32 + 31, and write sets name DC 31."""
+    batch = list(random_batch(600, 32, 0xEA6E + 32))
+    slots = {f * 32 + to for t, base, _ in batch if t == BC for f, to in base[0]}
+    dcs = {e[-1] for t, _, effs in batch if t == BC for e in effs}
+    assert max(slots) > 16 * 32 and 31 in dcs, "bases past slot 16 * n_dc, effects at DC 31"
+    check(mat, 32, batch)

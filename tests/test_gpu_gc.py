@@ -57,10 +57,11 @@ def _oracle_kept_ids(k, ops, thr):
     return [op[0] for _pos, op in sorted(kept)]
 
 
-@pytest.mark.parametrize("seed", range(4))
+@pytest.mark.parametrize("seed", range(6))
 def test_gpu_prune_ops_host_threshold(mat, seed):
+    """(seeds 4 and 5: 17 and 32 DCs, partial clocks -- am_store_update's widest scatter.)"""
     rng = random.Random(7100 + seed)
-    n_dc = [1, 3, 5, 8][seed]
+    n_dc = [1, 3, 5, 8, 17, 32][seed]
     partial = seed >= 2
     n_keys = 48
     keys, types = [], []
@@ -190,10 +191,29 @@ def test_gpu_gc_from_snapshot_cache(mat):
     GC (am_snapcache_gc_threshold) truncates every dict to its newest SNAPSHOT_MIN snapshots and
     their vectorclock:min prunes the log; later reads through the pruned log with the same
     cache -- low clocks (the cold path) included -- match the oracle."""
-    rng = random.Random(4242)
-    n_dc, n_keys = 3, 32
+    _gc_from_snapshot_cache(mat, 3, 4242, None)
+
+
+def test_gpu_gc_from_snapshot_cache_32_dcs(mat):
+    """The same at 32 DCs.  The first 55 % of every fourth key's ops neither name DC 31 in their
+    snapshot nor commit there, so some kept snapshot clocks lack DC 31 beside ones that hold it:
+    vectorclock:min reads the missing entry as 0 (oracle vc_min2).  am_snapcache_gc_threshold's own
+    output (mask, clock, presence with bit 31) is compared with the oracle's gc_threshold."""
+    _gc_from_snapshot_cache(mat, 32, 4243, 31)
+
+
+def _gc_from_snapshot_cache(mat, n_dc, seed, drop_dc):
+    from antidote_amd.materializer import _DevBuf
+    rng = random.Random(seed)
+    n_keys = 32
     types = [abi.AM_PN if k % 2 == 0 else abi.AM_LWW for k in range(n_keys)]
     keys = [randlog.rand_key_ops(rng, types[k], n_dc, rng.choice([0, 10, 60, 150, 300])) for k in range(n_keys)]
+    if drop_dc is not None:
+        for k in range(0, n_keys, 4):
+            for op in keys[k][:len(keys[k]) * 55 // 100]:
+                op.snap.pop(drop_dc)
+                if op.commit_dc == drop_dc:
+                    op.commit_dc = 0
     store = mat.store(HostLog(n_dc, keys, key_types=types))
     cache = mat.snapshot_cache(store, n_keys)
     st = R.VnodeState()
@@ -221,14 +241,30 @@ def test_gpu_gc_from_snapshot_cache(mat):
         for rnd in range(6):
             read_round(0.1 * rnd, 0.1 * rnd + 0.25)
         D0 = store.download()
+        dev_thr = None
+        if drop_dc is not None:  # the thresholds themselves (the call is idempotent: update repeats it)
+            bufs = [_DevBuf(mat, n_keys), _DevBuf(mat, n_keys * 8 * n_dc), _DevBuf(mat, n_keys * 4)]
+            abi.check(mat.L.am_snapcache_gc_threshold(mat.ctx, cache.handle, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr),
+                      "am_snapcache_gc_threshold")
+            dev_thr = (np.zeros(n_keys, np.uint8), np.zeros((n_dc, n_keys), np.uint64), np.zeros(n_keys, np.uint32))
+            for b, a in zip(bufs, dev_thr):
+                b.download(a)
+                b.free()
         s1, flags = store.update(prune=cache)
         D1 = s1.download()
+        uneven = 0
         for k, ops in enumerate(keys):
             if k not in st.snapshot_cache or st.snapshot_cache[k][1] == 0:
                 assert _key_ops(D1, k) == _key_ops(D0, k)
+                assert dev_thr is None or dev_thr[0][k] == 0
                 continue
             sub = R.vo_sublist(st.snapshot_cache[k], 1, R.SNAPSHOT_MIN)
             thr = R.gc_threshold(sub)
+            if dev_thr is not None:
+                assert dev_thr[0][k] == 1, k
+                got = {d: int(dev_thr[1][d, k]) for d in range(n_dc) if (int(dev_thr[2][k]) >> d) & 1}
+                assert got == thr, (k, got, thr)
+                uneven += len({frozenset(c) for c, _ in sub[0]}) > 1
             st.snapshot_cache[k] = sub  # snapshot_insert_gc stores PrunedSnapshots (:536)
             t = st.ops_cache.get(k)
             if t is None:
@@ -245,6 +281,7 @@ def test_gpu_gc_from_snapshot_cache(mat):
                 assert [i for i, _ in _key_ops(D1, k)] == [i for i, _ in kept_ops], k
             assert len(cur) == n
             st.ops_cache[k] = R.OpsTuple(k, len(kept_ops), t.element(2)[1], t.element(3), kept_ops)
+        assert drop_dc is None or uneven >= 1, "a key whose kept clocks differ in their DCs"
         cache.store = s1
         read_round(0.0, 0.3)  # below the kept snapshots: the cold path, on both sides
         for rnd in range(6, 11):

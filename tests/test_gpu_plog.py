@@ -107,12 +107,13 @@ def log3(mat):
     plog.close()
 
 
-@pytest.mark.parametrize("n_dc", [1, 3, 8, 16])
+@pytest.mark.parametrize("n_dc", [1, 3, 8, 16, 32])
 def test_gpu_plog_random_logs(mat, n_dc):
-    """All five types, every chain length, partial clocks and TxId reads on two of the widths, 3 %
-    bad effects, late transactions; a mixed batch of 65 reads with horizons on some."""
+    """All five types, every chain length, partial clocks and TxId reads on two of the widths (both
+    at 32, AM_MAX_DC: commit DC 31, presence bit 31), 3 % bad effects, late transactions; a mixed
+    batch of 65 reads with horizons on some."""
     rng = random.Random(9300 + n_dc)
-    partial, txids = n_dc in (3, 16), n_dc in (3, 8)
+    partial, txids = n_dc in (3, 16, 32), n_dc in (3, 8, 32)
     log = rand_log(rng, n_dc, partial, txids)
     cm = Commits(n_dc, log)
     assert cm.n_var > 0 and any(len(e) > 1 for _, _, _, _, effs in log for _, t, e in effs

@@ -47,12 +47,17 @@ def _dev_value(t, v0, v1, vflag):
 
 
 @pytest.mark.parametrize("t", [abi.AM_PN, abi.AM_LWW, abi.AM_AWSET, abi.AM_MVREG, abi.AM_BCOUNTER])
-@pytest.mark.parametrize("seed", range(3))
+@pytest.mark.parametrize("seed", range(4))
 def test_gpu_snapcache_internal_read(mat, seed, t):
     """Every type's values are cached (PN / LWW in the entry, set pairs and bounded-counter
-    slots in the value pool) and serve later reads as bases."""
+    slots in the value pool) and serve later reads as bases.  Seed 3 runs at 32 DCs (AM_MAX_DC:
+    the pool's reserved words are 32 * 32 + 32 + 1, a bounded-counter base has 1056 slots, entry
+    clocks carry bit 31), with twice the rounds in steps half as wide, so that some dict reaches
+    SNAPSHOT_THRESHOLD entries and snapshot_insert_gc prunes it to SNAPSHOT_MIN (asserted)."""
     rng = random.Random(3300 + seed + 17 * t)
-    n_dc = [1, 3, 5][seed]
+    n_dc = [1, 3, 5, 32][seed]
+    rounds, step = (12, 0.1) if seed < 3 else (24, 0.05)
+    shrunk = 0
     n_keys = 40
     keys, types = [], []
     for k in range(n_keys):
@@ -65,11 +70,12 @@ def test_gpu_snapcache_internal_read(mat, seed, t):
     st = _oracle_state(keys, types)
     hi = [ops[-1].commit_time if ops else 20 for ops in keys]
     try:
-        for rnd in range(12):
+        for rnd in range(rounds):
             sel = rng.sample(range(n_keys), 25)
+            sizes = {k: st.snapshot_cache[k][1] for k in sel if k in st.snapshot_cache}
             reads = []
             for k in sel:
-                q = min(1.3, 0.1 * rnd + rng.choice([0.0, 0.05, 0.2])) if rng.random() < 0.85 else rng.random() * 0.5
+                q = min(1.3, step * rnd + rng.choice([0.0, 0.05, 0.2])) if rng.random() < 0.85 else rng.random() * 0.5
                 c = int(10 + (hi[k] - 10) * q)
                 clock = {d: c + rng.randint(0, 3) for d in range(n_dc)}
                 reads.append(Read(k, types[k], clock))
@@ -90,6 +96,7 @@ def test_gpu_snapcache_internal_read(mat, seed, t):
                     assert g[0] == "ok" and g[1] == randlog.canon_state(rd.type, ref[1]), (rnd, rd, g, ref)
             for k in sel:
                 dev = cache.snapshots(k, types[k])
+                shrunk += k in sizes and st.snapshot_cache[k][1] < sizes[k]
                 if k not in st.snapshot_cache:
                     assert dev is None
                     continue
@@ -98,6 +105,7 @@ def test_gpu_snapcache_internal_read(mat, seed, t):
                 for (clock, snap), (dclock, dlo, dval) in zip(lst, dev):
                     assert dict(clock) == dclock, (rnd, k)
                     assert _canon_entry(types[k], snap) == (dlo, dval), (rnd, k, snap, dlo, dval)
+        assert seed < 3 or shrunk >= 1, "snapshot_insert_gc pruned a dict"
     finally:
         cache.close()
         store.close()

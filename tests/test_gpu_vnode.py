@@ -153,13 +153,15 @@ def _oracle_payload(op, key):
     return randlog.payload_term(op, key=key)
 
 
-@pytest.mark.parametrize("seed", range(3))
+@pytest.mark.parametrize("seed", range(4))
 def test_gpu_vnode_random(mat, seed):
     """Random insert batches (1-70 ops per key: GC triggers every 50 ids and on full tuples)
     and read batches (repeated keys, ShouldGC on some reads, old clocks that take the log
-    cold path) over keys of all five types, against the oracle's VnodeState."""
+    cold path) over keys of all five types, against the oracle's VnodeState.  Seed 3 runs at 32
+    DCs (AM_MAX_DC): the pool reserves 32 * 32 + 32 + 1 words per value, a bounded-counter base
+    has 1056 slots, and the GC thresholds carry bit 31."""
     rng = random.Random(9100 + seed)
-    n_dc = [1, 3, 4][seed]
+    n_dc = [1, 3, 4, 32][seed]
     types = [abi.AM_PN, abi.AM_LWW, abi.AM_AWSET, abi.AM_MVREG, abi.AM_BCOUNTER]
     n_keys = 20
     ktype = [types[k % 5] for k in range(n_keys)]

@@ -104,6 +104,53 @@ def test_c_oracle_vs_python_random(t, seed):
             _compare(oracle_one(ops, n_dc, read2), randlog.ref_materialize(t, ops, read2))
 
 
+@pytest.mark.parametrize("n_dc", [13, 17, 31, 32])
+@pytest.mark.parametrize("t", randlog.TYPES)
+@pytest.mark.parametrize("seed", range(3))
+def test_c_oracle_vs_python_wide(t, n_dc, seed):
+    """The same cross-check at the widths the device compiles as padded D = 16 (13), padded D = 32
+    (17, 31) and exact D = 32 (32: presence mask 0xFFFFFFFF, commit DC 31 in op_meta's five bits).
+    seed 0: full clocks with TxIds; seed 1: partial op and read clocks; seed 2: full clocks with
+    bad effects.  Half of a bounded counter's effects move rights among DCs 0, 16, 30, 31 and
+    n_dc - 1, so above 16 DCs P slots past 16 * n_dc and, at 32, the D slot n_dc^2 + 31 hold
+    values; the test asserts that they did."""
+    rng = random.Random(seed * 131 + 17 * t + n_dc)
+    partial, txids = seed == 1, seed == 0
+    p_hi = d_hi = -1
+    n_incl = 0
+    for trial in range(12):
+        ops = randlog.rand_key_ops(rng, t, n_dc, rng.randint(0, 40), partial=partial, txids=txids,
+                                   bad_rate=0.03 if seed == 2 else 0.0)
+        randlog.far_bc_effects(rng, n_dc, ops)
+        if t == abi.AM_BCOUNTER and len(ops) >= 2 and not (ops[0].bad or ops[1].bad):
+            ops[0].effect, ops[1].effect = ("decrement", 3, n_dc - 1), ("transfer", 4, 0, n_dc - 1)
+        hi = ops[-1].commit_time if ops else 20
+        # every DC's entry is drawn alone and the lowest one decides, so the range starts near the
+        # top, in the middle or at 0; a partial read clock lacks each DC with chance 0.5 / n_dc (an
+        # op is excluded when the clock lacks a DC its snapshot names: 0.2 would exclude all)
+        lo = [max(hi - 8, 0), hi // 2, 0][trial % 3]
+        clock = randlog.rand_clock(rng, n_dc, lo, hi + 5, partial=partial, miss=0.5 / n_dc)
+        read = Read(0, t, clock, rng.choice([None, 1, 2]) if txids else None)
+        got = oracle_one(ops, n_dc, read)
+        _compare(got, randlog.ref_materialize(t, ops, read))
+        if got[0] != "ok":
+            continue
+        n_incl += got[5]
+        clock2 = {d: v + rng.randint(0, 20) for d, v in clock.items()}
+        read2 = Read(0, t, clock2, None, got[3], got[2], got[1])
+        got2 = oracle_one(ops, n_dc, read2)
+        _compare(got2, randlog.ref_materialize(t, ops, read2))
+        if t == abi.AM_BCOUNTER:
+            for g in (got, got2):
+                if g[0] == "ok":
+                    p_hi = max([p_hi] + [f * n_dc + to for f, to in g[1][0]])
+                    d_hi = max([d_hi] + list(g[1][1]))
+    assert n_incl >= 10, n_incl  # a guard on the inputs: the first reads include ops at all
+    if t == abi.AM_BCOUNTER:
+        assert d_hi == n_dc - 1, d_hi
+        assert p_hi >= (n_dc - 1) * n_dc, p_hi  # a P slot of the last DC's row: past 16 * n_dc above 16
+
+
 def test_c_oracle_corrupted_and_empty():
     ops = [Op(abi.AM_PN, 0, 5, {0: 1}, 3)]
     r = oracle_one(ops, 1, Read(0, abi.AM_LWW, {0: 10}))
