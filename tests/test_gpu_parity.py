@@ -293,7 +293,10 @@ def _big_key_ops(rng, t, n_dc, n_ops, partial, txids, bad_rate, concurrent):
 def test_gpu_big_reads(mat, t, seed):
     """Set-CRDT reads beyond the LDS tier (thousands of ops: chunked over workgroups with
     local resolution + global hash), mixed with short reads of the same batch; partial
-    clocks, TxIds, cached bases, invalid effects, > 2048 survivors (global-memory sort)."""
+    clocks, TxIds, cached bases, invalid effects.  Only the MV keys made `concurrent` leave more
+    than 2048 survivors (k_big_finish's grouped write, and over the cached bases its global-memory
+    sort); the random AW keys hold 6 elements and a handful of live tokens, so the AW side of that
+    sort, the tier's list / hash overflows and the capacity edges are tests/test_gpu_big_exits.py's."""
     rng = random.Random(7000 + seed * 13 + t)
     n_dc = [2, 3, 8][seed]
     partial, txids = seed == 1, seed == 2
