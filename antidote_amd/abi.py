@@ -195,6 +195,7 @@ SIGNATURES = [
     ("am_store_destroy", c_int, [c_void_p]),
     ("am_store_index", c_int, [c_void_p, c_void_p, c_int]),
     ("am_store_view_stats", c_int, [c_void_p, c_void_p, POINTER(c_uint64)]),
+    ("am_store_lag_width", c_int, [c_void_p, c_void_p, c_void_p]),
     ("am_materialize", c_int, [c_void_p, POINTER(am_op_log), POINTER(am_read_batch), POINTER(am_read_result)]),
     ("am_materialize_host", c_int, [c_void_p, c_void_p, POINTER(am_read_batch), POINTER(am_read_result)]),
     ("am_gst_local_min", c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),

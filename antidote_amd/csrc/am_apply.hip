@@ -149,8 +149,10 @@ __device__ void zone_rewrite(const am_op_log &L, const am_op_log &S, uint64_t i,
 }
 
 // one wave per touched key: S's key i -> the store's key keys[i]
+// (lagw / s_lagw: the two stores' lag widths, am_store::lagw; null without the lag view)
 __global__ void __launch_bounds__(256) k_writeback(am_op_log L, am_op_log S, const uint64_t *s_counter,
-                                                   uint64_t *counter, const uint64_t *keys, uint64_t m, int zlevel) {
+                                                   uint64_t *counter, const uint64_t *keys, uint64_t m, int zlevel,
+                                                   uint16_t *lagw, const uint16_t *s_lagw) {
   __shared__ uint32_t zbits[4][2 * (AM_GRP_MAX_REC / 32)];  // per wave: a block's summary being rebuilt
   const uint32_t lane = threadIdx.x & (WAVE_SZ - 1);
   const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / WAVE_SZ);
@@ -211,6 +213,8 @@ __global__ void __launch_bounds__(256) k_writeback(am_op_log L, am_op_log S, con
       for (uint32_t d = lane; d < L.n_dc; d += WAVE_SZ)
         const_cast<int32_t *>(L.key_lag)[k * L.n_dc + d] =
             (S.key_lag && S.lag_ct && S.lag) ? S.key_lag[i * S.n_dc + d] : (d == 0 && n ? AM_LAG_ROUTED : 0);
+    // and its lag width, next to the row: S's over the merged key (0xFFFF where S gives none)
+    if (lagw && lane == 0) lagw[k] = (S.key_lag && S.lag_ct && S.lag && s_lagw) ? s_lagw[i] : (uint16_t)0xFFFFu;
     if (L.zone_vc)  // the blocks inside the key: maxima, marks and summaries recomputed
       zone_rewrite(L, S, i, d0, n, cap_end, L.rec_key_off ? L.rec_key_off[k] : 0, zlevel, lane,
                    zbits[threadIdx.x / WAVE_SZ]);
@@ -440,7 +444,8 @@ int am_store_apply_ex(am_ctx *c, am_store *st, uint64_t m, const uint64_t *d_key
   }
   if (!rc && fit) {
     hipLaunchKernelGGL(k_writeback, dim3(grid_waves(m)), dim3(256), 0, c->stream, L, S,
-                       (const uint64_t *)sub->counter, st->counter, d_keys, m, st->zone_level);
+                       (const uint64_t *)sub->counter, st->counter, d_keys, m, st->zone_level, st->lagw,
+                       (const uint16_t *)sub->lagw);
     if (hipGetLastError() != hipSuccess) rc = AM_ERR_HIP;
     if (!rc && h_new_len) {
       std::vector<uint64_t> so(m + 1);

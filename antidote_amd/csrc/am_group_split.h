@@ -33,6 +33,7 @@ __device__ __forceinline__ uint32_t wave_min_u32_v(uint32_t v) {
 // limits -- computed by the batch's lane j for read j, 32 reads in one pass and their keys' lag
 // bases in one load latency, and read back wave-uniform when the wave comes to the read.
 constexpr uint32_t SLOT_NEVER = 1u, SLOT_MISS = 2u;  // fl: PkRead::never, PkRead::miss != 0
+constexpr uint32_t SLOT_LW_SHIFT = 16;  // fl's upper half (LAG): the key's lag width, for the read loop's raise
 struct ISlotHead {
   uint64_t off0, K, idb;
   uint32_t r, nops;
@@ -149,17 +150,27 @@ __device__ __forceinline__ uint32_t mx_reduce(const uint32_t (*smx)[WAVE], uint3
 // five waves without a vector spill at D = 8 (at six, 80 VGPRs, it spills 9-12).  Packed (the
 // tile's D x 4 entries): 97 VGPRs at D = 8, four waves.  A read's set-up (thresholds, lag bases,
 // window limits) is not in the loop either: the batch's lane j computes read j's into the slot.
+//
+// The lag instantiation takes one more argument than the packed one (X: const uint16_t *lagw, the
+// store's per-key lag widths, am_internal.h am_lagw_find; null: 0xFFFF for every key).  The window
+// of a read is sized by its key's width (am_inclwin.h): lane j loads it with the key's lag bases,
+// so the slot's out_lim is the tight one, and the read loop takes it from the slot's fl for the
+// raise without loads.  The packed instantiation's argument block is as it was.
 #ifndef AM_INCL_WAVES
 #define AM_INCL_WAVES(D) 4
 #endif
 #ifndef AM_INCL_LAG_WAVES
 #define AM_INCL_LAG_WAVES(D) 5
 #endif
-template <int DMAX, int TYPE, bool EXACT, bool LAG>
+__device__ __forceinline__ const uint16_t *incl_lagw() { return nullptr; }
+__device__ __forceinline__ const uint16_t *incl_lagw(const uint16_t *p) { return p; }
+template <int DMAX, int TYPE, bool EXACT, bool LAG, class... X>
 __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL_WAVES(DMAX)) k_grp_incl(am_log_arg LA, am_read_batch B, am_read_result R, am_sel S,
                                                        am_retry next, am_retry routed, uint32_t short_opl,
-                                                       uint32_t *ibm, uint64_t *escr) {
+                                                       uint32_t *ibm, uint64_t *escr, X... xa) {
+  static_assert(sizeof...(X) == (LAG ? 1 : 0), "the lag instantiation takes the lag widths, the packed one nothing");
   const am_op_log L = LA.log();
+  const uint16_t *const lagw = incl_lagw(xa...);
   constexpr int OPL = 4;
   constexpr uint64_t TILE = (uint64_t)WAVE * OPL;
   constexpr uint32_t LPW = 32 / OPL;
@@ -210,14 +221,15 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
 #pragma unroll
           for (int d = 0; d < DMAX; ++d) lbk[d] = d < (int)nd ? (uint32_t)L.key_lag[mm.key * nd + d] : 0u;
         }
+        const uint32_t lw = (LAG && lagw) ? (uint32_t)lagw[mm.key] : (uint32_t)AM_IW_LAG_MAX;  // the key's lag width
         am_iw_read rs;
-        am_iw_read_setup(u.S, u.spres, u.allmask, K, LAG ? lbk : nullptr, nd, (uint32_t)DMAX, thr, &rs);
+        am_iw_read_setup_w(u.S, u.spres, u.allmask, K, LAG ? lbk : nullptr, nd, (uint32_t)DMAX, lw, thr, &rs);
         ISlot<DMAX, LAG> &w = sl[sl_];
         w.off0 = mm.off0, w.K = K, w.idb = L.key_id_base ? L.key_id_base[mm.key] : 1;
         w.r = (uint32_t)mm.r, w.nops = (uint32_t)(mm.off1 - mm.off0);
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) w.thr[d] = thr[d];
-        w.fl = (rs.never ? SLOT_NEVER : 0u) | (rs.miss ? SLOT_MISS : 0u);
+        w.fl = (rs.never ? SLOT_NEVER : 0u) | (rs.miss ? SLOT_MISS : 0u) | (LAG ? lw << SLOT_LW_SHIFT : 0u);
         if constexpr (LAG) {
 #pragma unroll
           for (int d = 0; d < DMAX; ++d) w.lb[d] = lbk[d];
@@ -277,6 +289,7 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
         // and a raise is a max, so min(cin_lim, max(in_lim, raise)) is the same value.
         const int32_t lbm = (int32_t)uniform_u32(sl[j].lbm);  // the smallest lag base: the rounds' bound in u32 above it
         const uint32_t cin_lim = uniform_u32(sl[j].cin_lim), out_lim = uniform_u32(sl[j].out_lim);
+        const uint32_t lw = sfl >> SLOT_LW_SHIFT;  // the key's lag width: a sure-in op c raises the bound to c - lw
         uint32_t in_lim = 0;
         const uint32_t lo = (uint32_t)(off0 - t0), nops = (uint32_t)(off1 - off0);  // the read's ops: [lo, lo + nops) from t0
         uint16_t *const list = sm.list;
@@ -304,7 +317,7 @@ __global__ void __launch_bounds__(BLOCK, LAG ? AM_INCL_LAG_WAVES(DMAX) : AM_INCL
                 if (q - lo < nops && c[k][i] < cin_lim) sure = max(sure, c[k][i] + 1u);
               }
             const uint32_t m = uniform_u32(wave_max_u32_v(sure));
-            if (m) in_lim = min(cin_lim, am_iw_lim_raise(in_lim, am_iw_lim_sure(m - 1u)));
+            if (m) in_lim = min(cin_lim, am_iw_lim_raise(in_lim, am_iw_lim_sure_w(m - 1u, lw)));
           }
           uint32_t nl = 0;  // list entries (wave-uniform)
           auto classify = [&](const int k, const uint32_t (&ck)[OPL]) {
@@ -920,7 +933,8 @@ int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_rea
   const uint64_t want = (B->n_reads + NW * IWB - 1) / (NW * IWB);  // a wave per IWB reads
   // the packed instantiation's grid, the first launch's, the record pass's
   const uint64_t bp = grp_grid(ctx, occ_i[0], k_grp_incl<D, TYPE, EXACT, false>, BLOCK, 0, 2, want);
-  const uint64_t bi = lag ? grp_grid(ctx, occ_i[1], k_grp_incl<D, TYPE, EXACT, true>, BLOCK, 0, 2, want) : bp;
+  const uint64_t bi =
+      lag ? grp_grid(ctx, occ_i[1], k_grp_incl<D, TYPE, EXACT, true, const uint16_t *>, BLOCK, 0, 2, want) : bp;
   const uint64_t bw = spans ? grp_grid(ctx, occ_s, k_grp_spans<D, TYPE>, BLOCK, 0, 1, want)
                             : grp_grid(ctx, occ_w, k_grp_recs<D, TYPE>, BLOCK, 0, 1, want);
   if (bi == 0) return AM_OK;
@@ -937,8 +951,11 @@ int launch_split(am_ctx *ctx, const am_op_log *L, const am_read_batch *B, am_rea
     am_retry routed;
     am_sel rsel;
     if (int rc = am_route_list(ctx, B->n_reads, &routed, &rsel)) return rc;
-    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, true>), dim3((unsigned)bi), dim3(BLOCK), 0, ctx->stream, *L, *B, *R,
-                       S, next, routed, short_opl, (uint32_t *)ibm, escr);
+    // the store's per-key lag widths when the log's lag view is a store's of this context (null:
+    // the format's 16 bits for every key)
+    const uint16_t *const lagw = am_lagw_find(ctx, L);
+    hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, true, const uint16_t *>), dim3((unsigned)bi), dim3(BLOCK), 0,
+                       ctx->stream, *L, *B, *R, S, next, routed, short_opl, (uint32_t *)ibm, escr, lagw);
     hipLaunchKernelGGL((k_grp_incl<D, TYPE, EXACT, false>), dim3((unsigned)bp), dim3(BLOCK), 0, ctx->stream, *L, *B,
                        *R, rsel, next, am_retry{}, short_opl, (uint32_t *)ibm, escr);
   } else {

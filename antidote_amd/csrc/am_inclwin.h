@@ -13,6 +13,13 @@
 // ops (0 before the first: entries are >= 0), or c' - lb_d - 0xFFFF of an op c' <= cin, which
 // gives cmax >= c' - 0xFFFF without a lag load.  Only ops with min(cin, cmax) < c <= hi (the
 // window) need their lags.  Exact in any visiting order; a stale, smaller cmax is always safe.
+//
+// 0xFFFF is the range of the lag's format.  Where a bound w of the key's own lags is known -- every
+// lag_d of every op of the key the view holds is <= w <= 0xFFFF (the store's per-key lag width) -- the
+// same argument holds with w in its place: hi = cin + w, and an op c' <= cin gives cmax >= c' - w
+// (taken as c' - max(w, 1): see am_iw_cmax_sure_w).
+// The *_w forms take the width; the others are the same functions at w = AM_IW_LAG_MAX, and any
+// upper bound of the lags is a safe width.
 #pragma once
 #include <stdint.h>
 
@@ -42,14 +49,21 @@ AM_IW_HD int64_t am_iw_fold(int64_t acc, uint32_t v, uint32_t lb) {
 }
 /* cin_fold: am_iw_fold over the thresholds of the DCs d < nd.  never (PkRead::never): no op
  * passes and nothing needs lags. */
-AM_IW_HD void am_iw_init(am_inclwin *w, int64_t cin_fold, int never) {
-  const int64_t cin = (never || cin_fold == AM_IW_NOBOUND) ? -1 - AM_IW_LAG_MAX : cin_fold;
-  w->cin = cin, w->hi = cin + AM_IW_LAG_MAX, w->cmax = -1;
+AM_IW_HD void am_iw_init_w(am_inclwin *w, int64_t cin_fold, int never, uint32_t lw) {
+  const int64_t cin = (never || cin_fold == AM_IW_NOBOUND) ? -1 - (int64_t)lw : cin_fold;
+  w->cin = cin, w->hi = cin + (int64_t)lw, w->cmax = -1;
 }
-AM_IW_HD void am_iw_setup(am_inclwin *w, const uint32_t *thr, const uint32_t *lb, uint32_t nd, int never) {
+AM_IW_HD void am_iw_init(am_inclwin *w, int64_t cin_fold, int never) {
+  am_iw_init_w(w, cin_fold, never, (uint32_t)AM_IW_LAG_MAX);
+}
+AM_IW_HD void am_iw_setup_w(am_inclwin *w, const uint32_t *thr, const uint32_t *lb, uint32_t nd, int never,
+                            uint32_t lw) {
   int64_t f = AM_IW_NOBOUND;
   for (uint32_t d = 0; d < nd; ++d) f = am_iw_fold(f, thr[d], lb[d]);
-  am_iw_init(w, f, never);
+  am_iw_init_w(w, f, never, lw);
+}
+AM_IW_HD void am_iw_setup(am_inclwin *w, const uint32_t *thr, const uint32_t *lb, uint32_t nd, int never) {
+  am_iw_setup_w(w, thr, lb, nd, never, (uint32_t)AM_IW_LAG_MAX);
 }
 
 /* the bound a set of running maxima m[] (over included ops; 0 where none yet) gives */
@@ -58,8 +72,11 @@ AM_IW_HD int64_t am_iw_cmax_of(const uint32_t *m, const uint32_t *lb, uint32_t n
   for (uint32_t d = 0; d < nd; ++d) f = am_iw_fold(f, m[d], lb[d]);
   return nd ? f : -1;
 }
-/* the bound an op with c <= cin gives without its lags */
-AM_IW_HD int64_t am_iw_cmax_sure(uint32_t c) { return (int64_t)c - AM_IW_LAG_MAX; }
+/* the bound an op with c <= cin gives without its lags (lw: the key's lag width): c - lw, and
+ * below c itself -- the maxima are folded over the window ops alone, so the op that gives the bound
+ * has to stay in the window (at lw = 0, where its entries ARE the maxima, the bound is c - 1) */
+AM_IW_HD int64_t am_iw_cmax_sure_w(uint32_t c, uint32_t lw) { return (int64_t)c - (int64_t)(lw ? lw : 1u); }
+AM_IW_HD int64_t am_iw_cmax_sure(uint32_t c) { return am_iw_cmax_sure_w(c, (uint32_t)AM_IW_LAG_MAX); }
 AM_IW_HD void am_iw_raise(am_inclwin *w, int64_t cmax) { w->cmax = cmax > w->cmax ? cmax : w->cmax; }
 
 /* The bound of running maxima in u32, for the rounds of the inclusion pass (one op per lane): one
@@ -99,8 +116,14 @@ AM_IW_HD int am_iw_class32(uint32_t c, uint32_t in_lim, uint32_t out_lim) {
  * with cin_lim = am_iw_lim(cin) and cmax_lim = am_iw_lim(cmax): cmax_lim starts at 0 (cmax = -1) and
  * a raise is a u32 max with the limit of the new bound, which the two kinds of raise give in 32 bits:
  *   am_iw_lim_sure(c)      == am_iw_lim(am_iw_cmax_sure(c))       c <= 2^32 - 2 a sure-in commit word
+ *                             (am_iw_lim_sure_w(c, lw) == am_iw_lim(am_iw_cmax_sure_w(c, lw)) likewise)
  *   am_iw_lim_of32(f, lbm) == am_iw_lim(am_iw_cmax_of32(f, lbm))  f the lanes' largest am_iw_fold32 */
-AM_IW_HD uint32_t am_iw_lim_sure(uint32_t c) { return c > 0xFFFEu ? c - 0xFFFEu : 0u; }
+/* (with m = max(lw, 1): c - m + 1 <= c <= 2^32 - 2, no carry and no saturation to apply) */
+AM_IW_HD uint32_t am_iw_lim_sure_w(uint32_t c, uint32_t lw) {
+  const uint32_t m = lw ? lw : 1u;
+  return c >= m ? c - m + 1u : 0u;
+}
+AM_IW_HD uint32_t am_iw_lim_sure(uint32_t c) { return am_iw_lim_sure_w(c, (uint32_t)AM_IW_LAG_MAX); }
 AM_IW_HD uint32_t am_iw_lim_of32(uint32_t f, int32_t lbm) {
   if (lbm >= 0) {
     const uint32_t s = f + (uint32_t)lbm;
@@ -131,8 +154,9 @@ typedef struct am_iw_read {
 AM_IW_HD uint32_t am_iw_thr(uint64_t s, uint64_t K) {
   return s < K ? 0u : (s - K >= (uint64_t)AM_IW_ESC ? AM_IW_ESC - 1u : (uint32_t)(s - K));
 }
-AM_IW_HD void am_iw_read_setup(const uint64_t *S, uint32_t spres, uint32_t allmask, uint64_t K, const uint32_t *lb,
-                               uint32_t nd, uint32_t dmax, uint32_t *thr, am_iw_read *o) {
+/* lw: the key's lag width (am_inclwin.h's opening comment); out_lim is the limit of cin + lw */
+AM_IW_HD void am_iw_read_setup_w(const uint64_t *S, uint32_t spres, uint32_t allmask, uint64_t K, const uint32_t *lb,
+                                 uint32_t nd, uint32_t dmax, uint32_t lw, uint32_t *thr, am_iw_read *o) {
   int64_t f = 0; /* am_iw_fold over the DCs d < nd, from DC 0's term (no 64-bit start value to hold) */
   int32_t lbm = INT32_MAX;
   const int miss = (allmask & ~spres) != 0;
@@ -153,7 +177,11 @@ AM_IW_HD void am_iw_read_setup(const uint64_t *S, uint32_t spres, uint32_t allma
     }
   }
   am_inclwin w;
-  am_iw_init(&w, (lb && nd) ? f : AM_IW_NOBOUND, never);
+  am_iw_init_w(&w, (lb && nd) ? f : AM_IW_NOBOUND, never, lw);
   o->never = never, o->miss = miss, o->lbm = lbm;
   o->cin_lim = am_iw_lim(w.cin), o->out_lim = am_iw_lim(w.hi);
+}
+AM_IW_HD void am_iw_read_setup(const uint64_t *S, uint32_t spres, uint32_t allmask, uint64_t K, const uint32_t *lb,
+                               uint32_t nd, uint32_t dmax, uint32_t *thr, am_iw_read *o) {
+  am_iw_read_setup_w(S, spres, allmask, K, lb, nd, dmax, (uint32_t)AM_IW_LAG_MAX, thr, o);
 }

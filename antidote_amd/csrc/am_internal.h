@@ -60,7 +60,24 @@ struct am_ctx {
   hipEvent_t ev_fork = nullptr;
   // the CRDT types present in a log's keys, by key_type array: {n_keys, 1 << type mask}
   std::unordered_map<const void *, std::pair<uint64_t, uint32_t>> type_masks;
+  // The stores' per-key lag widths (am_store::lagw), by the key_lag row of the lag view they bound:
+  // a reader holds only (ctx, am_op_log) and finds the column here (am_lagw_find).  Kept on the
+  // top context (parent: a sub-context's owner), under its own mutex: published by the builder of
+  // a store's lag view, forgotten by am_store_destroy.
+  struct lagw_entry {
+    const void *lag_ct, *lag;
+    const uint16_t *lagw;
+  };
+  std::unordered_map<const void *, lagw_entry> lagw;
+  std::mutex lagw_mu;
+  am_ctx *parent = nullptr;
 };
+// the lag-width registry (am_runtime.hip).  am_lagw_find: the widths of the keys of L's lag view when
+// L's three lag columns are a store's of this context, as published; else null (a caller-built log,
+// or a copied key_lag row: readers then take the format's 16 bits)
+void am_lagw_publish(am_ctx *c, const am_op_log &L, const uint16_t *lagw);
+void am_lagw_forget(am_ctx *c, const void *key_lag);
+const uint16_t *am_lagw_find(am_ctx *c, const am_op_log *L);
 // sub-context i of c (created on first use; null on failure, error set)
 am_ctx *am_ctx_sub(am_ctx *c, int i);
 #define AM_LOCK(ctxp) std::lock_guard<std::recursive_mutex> am_lock_((ctxp)->mu)
@@ -119,6 +136,11 @@ struct am_store {
   uint64_t *counter = nullptr;   // [n_keys] OpCounter (ops-cache tuple element 3) after
                                  // am_store_update; null => the newest op's id
   int zone_level = AM_INDEX_SUMMARIES;  // the zone index it keeps (am_store_index)
+  // [n_keys] the key's lag width, with the lag view (else null): an upper bound of lag[d][p] over
+  // the key's ops the view holds (lag_ct[p] != AM_PK_ESC) and d < n_dc -- the builders write the
+  // maximum; 0xFFFF for a packed-routed key and a key with no op in the view.  Not in am_op_log
+  // (the ABI's): readers reach it through the context's registry (am_lagw_find)
+  uint16_t *lagw = nullptr;
 };
 // zone_vc rows after the n_dc maxima: exact mark, summary offset, records end, records begin,
 // summary slot (include/antidote_mat.h)

@@ -240,7 +240,9 @@ int build_esc_rows(am_store *st) {
 //      pass 3: the key's routing (include/antidote_mat.h AM_LAG_ROUTED): when its lag-only
 //      escapes exceed AM_LAG_ROUTE_NUM / AM_LAG_ROUTE_DEN of its packed ops, or a lag base
 //      does not fit int32, key_lag[k][0] = AM_LAG_ROUTED and every op's lag_ct = AM_PK_ESC:
-//      readers stream the key's packed view instead of walking its escapes op by op ----
+//      readers stream the key's packed view instead of walking its escapes op by op.
+//      Pass 2 also folds the key's lag width (am_store::lagw): the largest lag of the ops the view
+//      holds; 0xFFFF for a routed key and a key with no op in the view ----
 constexpr uint32_t LAG_MAX_DC = 16;
 
 // one key's lag classification, shared by the builder and the counters (am_store_view_stats)
@@ -281,7 +283,7 @@ __device__ __forceinline__ bool lag_routed(uint64_t n_packed, uint64_t n_lag_onl
   return n_packed && (!fit || n_lag_only * AM_LAG_ROUTE_DEN > n_packed * AM_LAG_ROUTE_NUM);
 }
 
-__global__ void k_lag(am_op_log L, uint32_t *lag_ct, uint16_t *lag, int32_t *key_lag) {
+__global__ void k_lag(am_op_log L, uint32_t *lag_ct, uint16_t *lag, int32_t *key_lag, uint16_t *lagw) {
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / WAVE);
   const uint64_t stride = L.snap_stride ? L.snap_stride : L.n_ops;
@@ -291,19 +293,28 @@ __global__ void k_lag(am_op_log L, uint32_t *lag_ct, uint16_t *lag, int32_t *key
     LagKey lk;
     lag_bases(L, stride, o0, o1, lane, lk);
     uint32_t npk = 0, nlo = 0;  // this lane's packed ops, and its lag-only escapes
+    uint32_t lmax = 0;          // this lane's largest lag over the ops the view holds
     for (uint64_t p = o0 + lane; p < o1; p += WAVE) {
       const bool pk = L.pk_vc[p] != AM_PK_ESC;
-      uint32_t c = 0;
+      uint32_t c = 0, lop = 0;  // (lop: the op's largest lag; lag_op zeroes the lags from the first that does not fit)
       bool ok = false;
-      if (pk) ok = lag_op(L, stride, p, lk, c, [&](uint32_t d, uint16_t l) { lag[(uint64_t)d * stride + p] = l; });
+      if (pk)
+        ok = lag_op(L, stride, p, lk, c, [&](uint32_t d, uint16_t l) {
+          lag[(uint64_t)d * stride + p] = l;
+          lop = l > lop ? l : lop;
+        });
+      if (ok) lmax = lop > lmax ? lop : lmax;
       if (!ok)
         for (uint32_t d = 0; d < nd; ++d) lag[(uint64_t)d * stride + p] = 0;
       lag_ct[p] = ok ? c : AM_PK_ESC;
       npk += pk, nlo += pk && !ok;
     }
-    const bool routed = lag_routed(wave_sum_u32(npk), wave_sum_u32(nlo), lk.fit);
+    const uint32_t tpk = wave_sum_u32(npk), tlo = wave_sum_u32(nlo);
+    const bool routed = lag_routed(tpk, tlo, lk.fit);
     if (routed)
       for (uint64_t p = o0 + lane; p < o1; p += WAVE) lag_ct[p] = AM_PK_ESC;
+    const uint32_t wmax = (uint32_t)wave_max_u64(lmax);
+    if (lane == 0) lagw[k] = (uint16_t)((routed || tpk == tlo) ? 0xFFFFu : wmax);
     for (uint32_t d = lane; d < nd; d += WAVE)
       key_lag[k * nd + d] = routed && d == 0 ? AM_LAG_ROUTED : (lk.fit ? (int32_t)lk.lb[d] : 0);
   }
@@ -354,15 +365,20 @@ int build_lag(am_store *st) {
   st->allocs.push_back(lg);
   if (int rc = am_dev_alloc(c, d.n_keys * d.n_dc * 4 + 16, &kl)) return rc;
   st->allocs.push_back(kl);
+  void *lw = nullptr;
+  if (int rc = am_dev_alloc(c, d.n_keys * 2 + 16, &lw)) return rc;
+  st->allocs.push_back(lw);
   // free slots (room for appends, padding) stay escaped: 0xFF bytes
   AM_HIP(hipMemsetAsync(ct, 0xFF, stride * 4 + 16, c->stream));
   AM_HIP(hipMemsetAsync(lg, 0, (size_t)d.n_dc * stride * 2 + 16, c->stream));
   const uint64_t blocks = (d.n_keys + 3) / 4 < 65536 ? (d.n_keys + 3) / 4 : 65536;
   hipLaunchKernelGGL(k_lag, dim3((unsigned)blocks), dim3(256), 0, c->stream, d, (uint32_t *)ct, (uint16_t *)lg,
-                     (int32_t *)kl);
+                     (int32_t *)kl, (uint16_t *)lw);
   AM_HIP(hipGetLastError());
   AM_HIP(hipStreamSynchronize(c->stream));
   d.lag_ct = (const uint32_t *)ct, d.lag = (const uint16_t *)lg, d.key_lag = (const int32_t *)kl;
+  st->lagw = (uint16_t *)lw;
+  am_lagw_publish(c, d, st->lagw);  // the view is published: its readers find the widths by its key_lag row
   return AM_OK;
 }
 

@@ -107,6 +107,7 @@ am_ctx *am_ctx_sub(am_ctx *c, int i) {
   s->device = c->device;
   s->n_cu = c->n_cu;
   s->is_sub = true;
+  s->parent = c->parent ? c->parent : c;
   s->stats = c->stats;
   if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&s->ev0, hipEventDisableTiming) != hipSuccess ||
@@ -142,6 +143,29 @@ int am_ctx_scratch(am_ctx *c, int slot, size_t bytes, void **out) {
   }
   *out = c->scratch[slot];
   return AM_OK;
+}
+
+// ---- the lag-width registry (am_internal.h): key_lag row -> the store's width column ----
+static am_ctx *lagw_top(am_ctx *c) { return c->parent ? c->parent : c; }
+void am_lagw_publish(am_ctx *c, const am_op_log &L, const uint16_t *lagw) {
+  if (!c || !L.key_lag || !lagw) return;
+  am_ctx *t = lagw_top(c);
+  std::lock_guard<std::mutex> g(t->lagw_mu);
+  t->lagw[L.key_lag] = am_ctx::lagw_entry{L.lag_ct, L.lag, lagw};
+}
+void am_lagw_forget(am_ctx *c, const void *key_lag) {
+  if (!c || !key_lag) return;
+  am_ctx *t = lagw_top(c);
+  std::lock_guard<std::mutex> g(t->lagw_mu);
+  t->lagw.erase(key_lag);
+}
+const uint16_t *am_lagw_find(am_ctx *c, const am_op_log *L) {
+  if (!c || !L || !L->key_lag) return nullptr;
+  am_ctx *t = lagw_top(c);
+  std::lock_guard<std::mutex> g(t->lagw_mu);
+  const auto it = t->lagw.find(L->key_lag);
+  if (it == t->lagw.end() || it->second.lag_ct != L->lag_ct || it->second.lag != L->lag) return nullptr;
+  return it->second.lagw;
 }
 
 // layout: words 0, 1 = the selection's range {0, count}; the list from word 4 (16-byte aligned)
@@ -275,6 +299,7 @@ int am_store_destroy(am_store *st) {
   if (!st) return AM_OK;
   AM_LOCK(st->ctx);
   (void)hipSetDevice(st->ctx->device);
+  am_lagw_forget(st->ctx, st->dev.key_lag);  // before its block can be handed out again
   for (void *p : st->allocs) am_dev_release(st->ctx, p);  // kept for the next store's columns
   delete st;
   return AM_OK;
@@ -348,6 +373,20 @@ int am_store_create(am_ctx *c, const am_op_log *h, am_store **out) {
 int am_store_log(const am_store *st, am_op_log *out) {
   if (!st || !out) return AM_ERR_INVALID;
   *out = st->dev;
+  return AM_OK;
+}
+
+int am_store_lag_width(am_ctx *c, const am_store *st, uint16_t *host_out) {
+  if (!c || !st || st->ctx != c || !host_out) return AM_ERR_INVALID;
+  AM_LOCK(c);
+  if (!st->lagw || !st->dev.key_lag) {
+    am_set_error("am_store_lag_width: the store has no lag view");
+    return AM_ERR_INVALID;
+  }
+  if (!st->dev.n_keys) return AM_OK;
+  AM_HIP(hipSetDevice(c->device));
+  AM_HIP(hipMemcpyAsync(host_out, st->lagw, st->dev.n_keys * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  AM_HIP(hipStreamSynchronize(c->stream));
   return AM_OK;
 }
 

@@ -98,6 +98,14 @@ class Store:
         abi.check(self.mat.L.am_store_view_stats(self.mat.ctx, self.handle, out), "am_store_view_stats")
         return dict(zip(abi.VIEW_STATS, (int(x) for x in out)))
 
+    def lag_width(self):
+        """The store's per-key lag widths (am_store_lag_width) as a numpy u16 array [n_keys];
+        raises on a store without a lag view."""
+        import numpy as np
+        out = np.zeros(max(1, int(self.device_log().n_keys)), np.uint16)
+        abi.check(self.mat.L.am_store_lag_width(self.mat.ctx, self.handle, out.ctypes.data), "am_store_lag_width")
+        return out[: int(self.device_log().n_keys)]
+
     def reserve(self) -> "Store":
         """A copy with room for appends per key (am_store_reserve), the layout am_store_apply
         updates in place."""

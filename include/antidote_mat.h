@@ -289,7 +289,12 @@ typedef struct am_op_log {
    *    its lag columns are unspecified.  Readers test the mark before using the row and stream
    *    the key's packed view.
    * Maintained by every writer (am_store_apply rewrites a touched key's columns and its key_lag
-   * row, mark included, and sets lag_ct = AM_PK_ESC on the slots a shrunk key frees). */
+   * row, mark included, and sets lag_ct = AM_PK_ESC on the slots a shrunk key frees).
+   * A store also keeps, outside this struct, each key's lag width: an upper bound of the lags of
+   * the key's ops the view holds (am_store_lag_width).  A read of the store's own log -- these
+   * three pointers as am_store_log gives them, on the store's context -- sizes its commit-word
+   * window by it; any other log (caller-built, or with a copied key_lag row) is read with the
+   * format's 16 bits.  The results are the same either way. */
   const uint32_t *lag_ct;      /* [snap_stride]                                       */
   const uint16_t *lag;         /* [n_dc][snap_stride]                                 */
   const int32_t *key_lag;      /* [n_keys][n_dc]                                      */
@@ -459,6 +464,11 @@ int am_store_index(am_ctx *ctx, am_store *st, int level);
 #define AM_VIEW_STAT_ROUTED_OPS 4    /* ops of those keys                                     */
 #define AM_VIEW_STAT_N 5
 int am_store_view_stats(am_ctx *ctx, const am_store *st, uint64_t out[AM_VIEW_STAT_N]);
+/* The store's per-key lag widths -> host_out [n_keys]: for each key an upper bound (as built: the
+ * maximum) of lag[d][p] over its ops in the lag view (lag_ct[p] != AM_PK_ESC) and d < n_dc; 0xFFFF
+ * for a packed-routed key and a key with no op in the view.  Current after am_store_apply; blocks
+ * until done.  AM_ERR_INVALID for a store without a lag view. */
+int am_store_lag_width(am_ctx *ctx, const am_store *st, uint16_t *host_out);
 
 /* ---- the hot path ---- */
 /* Device pointers; runs on the ctx stream.  Asynchronous except for two data-dependent
