@@ -34,6 +34,9 @@ AM_ERR_UNEXPECTED_OPERATION = 2
 AM_ERR_OVERFLOW = 3
 AM_ERR_CAPACITY = 4
 AM_ERR_NO_PERMISSIONS = 6  # {error, no_permissions} (am_generate_downstream)
+AM_ERR_WRITE_CONFLICT = 7  # {error, write_conflict} (am_cert_prepare)
+AM_ERR_NO_UPDATES = 8  # {error, no_updates} (am_cert_prepare / am_cert_finish)
+AM_CERT_SPIN_WAIT_MS = 10
 AM_ERR_INVALID = -1
 AM_ERR_UNSUPPORTED = -5
 AM_FLAG_MISSING_DC_LOGGED = 0x1
@@ -130,6 +133,21 @@ class am_commit_log(ctypes.Structure):
         ("op_meta", c_void_p), ("commit_time", c_void_p), ("snap_vc", c_void_p), ("snap_pres", c_void_p),
         ("op_txid", c_void_p), ("p0", c_void_p), ("p1", c_void_p), ("var_off", c_void_p), ("var_data", c_void_p),
         ("src", c_void_p),
+    ]
+
+
+class am_prepares(ctypes.Structure):
+    _fields_ = [
+        ("n_tx", c_uint64), ("n_pairs", c_uint64),
+        ("txid", c_void_p), ("start_time", c_void_p), ("prepare_time", c_void_p), ("certify", c_void_p),
+        ("key_off", c_void_p), ("key", c_void_p),
+    ]
+
+
+class am_finishes(ctypes.Structure):
+    _fields_ = [
+        ("n_tx", c_uint64), ("n_pairs", c_uint64),
+        ("txid", c_void_p), ("commit_time", c_void_p), ("committed", c_void_p), ("key_off", c_void_p), ("key", c_void_p),
     ]
 
 
@@ -270,6 +288,20 @@ SIGNATURES = [
     ("am_plog_read_host", c_int, [c_void_p, c_void_p, POINTER(am_read_batch), c_void_p, POINTER(am_read_result)]),
     ("am_vnode_create_logged", c_int, [c_void_p, c_uint32, c_uint64, POINTER(c_void_p)]),
     ("am_vnode_log", c_int, [c_void_p, POINTER(c_void_p)]),
+    ("am_cert_create", c_int, [c_void_p, c_uint64, c_uint64, c_int, POINTER(c_void_p)]),
+    ("am_cert_destroy", c_int, [c_void_p]),
+    ("am_cert_reserve", c_int, [c_void_p, c_uint64, c_uint64]),
+    ("am_cert_prepare", c_int, [c_void_p, POINTER(am_prepares), c_void_p]),
+    ("am_cert_prepare_host", c_int, [c_void_p, POINTER(am_prepares), c_void_p]),
+    ("am_cert_finish", c_int, [c_void_p, POINTER(am_finishes), c_void_p]),
+    ("am_cert_finish_host", c_int, [c_void_p, POINTER(am_finishes), c_void_p]),
+    ("am_cert_read_ready", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p]),
+    ("am_cert_read_ready_host", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p]),
+    ("am_cert_min_prepared", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_int)]),
+    ("am_cert_key_info", c_int, [c_void_p, c_uint64, POINTER(c_uint64), c_uint64, c_void_p, c_void_p,
+                                 POINTER(c_uint64)]),
+    ("am_cert_size", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("am_cert_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("am_codec_create", c_int, [POINTER(c_void_p)]),
     ("am_codec_destroy", c_int, [c_void_p]),
     ("am_codec_intern", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),

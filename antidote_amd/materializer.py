@@ -21,7 +21,7 @@ import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from . import abi
-from .oplog import Commits, Effects, HostBatch, HostLog, Op, Read, Updates, WriteSet
+from .oplog import Commits, Effects, Finishes, HostBatch, HostLog, Op, Prepares, Read, Updates, WriteSet
 
 IGNORE = None
 
@@ -538,6 +538,98 @@ class Vnode:
             self.handle = ctypes.c_void_p()
 
 
+class Certifier:
+    """The partition's write-write certification in HBM (am_cert): prepared_tx and committed_tx of
+    clocksi_vnode (src/clocksi_vnode.erl:450-632) and the read servers' two checks
+    (src/clocksi_readitem_server.erl:236-264), for batches.  Arguments and returns are CertSim's
+    (tests/certsim.py).  A call that fails raises abi.AmError with the code in .rc (AM_ERR_INVALID: a
+    malformed batch; AM_ERR_CAPACITY: more live entries than cap_entries or more committed keys than
+    cap_keys) and leaves the tables as they were; only reserve() changes the capacities."""
+
+    def __init__(self, mat: "Materializer", cap_keys: int, cap_entries: int, record_commits: bool = True):
+        self.mat, self.handle = mat, ctypes.c_void_p()
+        self._check(mat.L.am_cert_create(mat.ctx, cap_keys, cap_entries, 1 if record_commits else 0,
+                                         ctypes.byref(self.handle)), "am_cert_create")
+
+    @staticmethod
+    def _check(rc: int, what: str):
+        if rc != 0:
+            msg = abi.lib().am_last_error()
+            e = abi.AmError(f"{what} failed rc={rc}: {msg.decode() if msg else ''}")
+            e.rc = rc
+            raise e
+
+    def prepare(self, txs) -> List[int]:
+        """[(txid, start_time, prepare_time, certify, [key, ...])] (or a Prepares) -> statuses: AM_OK,
+        AM_ERR_WRITE_CONFLICT or AM_ERR_NO_UPDATES, as if served one at a time in batch order."""
+        import numpy as np
+        b = txs if isinstance(txs, Prepares) else Prepares(txs)
+        s, st = b.as_struct(), np.zeros(max(b.n_tx, 1), np.int32)
+        self._check(self.mat.L.am_cert_prepare_host(self.handle, ctypes.byref(s), st.ctypes.data), "am_cert_prepare_host")
+        return [int(x) for x in st[:b.n_tx]]
+
+    def finish(self, txs) -> List[int]:
+        """[(txid, commit_time, committed, [key, ...])] (or a Finishes) -> statuses: AM_OK or
+        AM_ERR_NO_UPDATES.  commit/5 with committed, abort/2 without."""
+        import numpy as np
+        b = txs if isinstance(txs, Finishes) else Finishes(txs)
+        s, st = b.as_struct(), np.zeros(max(b.n_tx, 1), np.int32)
+        self._check(self.mat.L.am_cert_finish_host(self.handle, ctypes.byref(s), st.ctypes.data), "am_cert_finish_host")
+        return [int(x) for x in st[:b.n_tx]]
+
+    def read_ready(self, reads, now: int) -> List[int]:
+        """[(key, start_time)] -> the wait in ms before each read may be served (0: ready)."""
+        import numpy as np
+        n = len(reads)
+        k = np.asarray([int(r[0]) for r in reads] or [0], np.uint64)
+        t = np.asarray([int(r[1]) for r in reads] or [0], np.uint64)
+        w = np.zeros(max(n, 1), np.uint64)
+        self._check(self.mat.L.am_cert_read_ready_host(self.handle, n, k.ctypes.data, t.ctypes.data, int(now),
+                                                       w.ctypes.data), "am_cert_read_ready_host")
+        return [int(x) for x in w[:n]]
+
+    def min_prepared(self) -> Optional[int]:
+        t, p = ctypes.c_uint64(), ctypes.c_int()
+        self._check(self.mat.L.am_cert_min_prepared(self.handle, ctypes.byref(t), ctypes.byref(p)), "am_cert_min_prepared")
+        return int(t.value) if p.value else None
+
+    def key_info(self, key: int):
+        """(commit time or 0, [(txid, prepare time)] sorted by (time, txid))."""
+        import numpy as np
+        cap = 64
+        while True:
+            ct, n = ctypes.c_uint64(), ctypes.c_uint64()
+            tx, tm = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+            rc = self.mat.L.am_cert_key_info(self.handle, int(key), ctypes.byref(ct), cap, tx.ctypes.data, tm.ctypes.data,
+                                             ctypes.byref(n))
+            if rc == abi.AM_ERR_CAPACITY and n.value > cap:
+                cap = int(n.value)
+                continue
+            self._check(rc, "am_cert_key_info")
+            return int(ct.value), [(int(tx[i]), int(tm[i])) for i in range(int(n.value))]
+
+    def reserve(self, cap_keys: int, cap_entries: int):
+        self._check(self.mat.L.am_cert_reserve(self.handle, cap_keys, cap_entries), "am_cert_reserve")
+
+    def size(self) -> Tuple[int, int, int, int]:
+        """(committed keys, live prepared entries, cap_keys, cap_entries)"""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        self._check(self.mat.L.am_cert_size(self.handle, *[ctypes.byref(x) for x in v]), "am_cert_size")
+        return tuple(int(x.value) for x in v)
+
+    def stats(self) -> Dict[str, int]:
+        """Counters since create: resolve rounds, status-block readbacks, compactions."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        self._check(self.mat.L.am_cert_stats(self.handle, *[ctypes.byref(x) for x in v]), "am_cert_stats")
+        return dict(zip(("rounds", "readbacks", "compactions"), (int(x.value) for x in v)))
+
+    def close(self):
+        if self.handle:
+            if self.mat.ctx:
+                self.mat.L.am_cert_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+
 class Materializer:
     """A context on one GPU (device index = local rank)."""
 
@@ -596,6 +688,9 @@ class Materializer:
 
     def vnode(self, n_dc: int, n_keys: int, logged: bool = False) -> Vnode:
         return Vnode(self, n_dc, n_keys, logged)
+
+    def certifier(self, cap_keys: int, cap_entries: int, record_commits: bool = True) -> Certifier:
+        return Certifier(self, cap_keys, cap_entries, record_commits)
 
     def partition_log(self, n_dc: int, cap_tx: int = 1024, cap_eff: int = 4096, cap_var: int = 4096) -> PartitionLog:
         return PartitionLog(self, n_dc, cap_tx, cap_eff, cap_var)

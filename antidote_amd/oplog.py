@@ -701,3 +701,95 @@ class Commits:
             "var_data": np.concatenate(words + [np.zeros(0, U64)]).astype(U64),
             "src": order.astype(np.uint32),
         }
+
+
+def _pair_columns(write_sets):
+    """key_off [n_tx+1] and key [n_pairs] of a batch's write sets, in batch order."""
+    key_off = np.zeros(len(write_sets) + 1, U64)
+    if write_sets:
+        key_off[1:] = np.cumsum([len(w) for w in write_sets], dtype=U64)
+    keys = [_u64(k) for w in write_sets for k in w]
+    return key_off, np.asarray(keys or [0], U64), len(keys)
+
+
+class Prepares:
+    """am_prepares in host memory: a batch of clocksi_vnode:prepare/6 requests in the order the vnode
+    serves them.  txs: [(txid, start_time, prepare_time, certify, [key, ...])], the tuples
+    CertSim.prepare takes; keys, TxIds and times are any u64.  A write set keeps its repeats (the
+    certifier enters a key once)."""
+
+    def __init__(self, txs: Sequence[Tuple[int, int, int, bool, Sequence[int]]]):
+        txs = [(int(x), int(s), int(p), bool(c), [int(k) for k in ks]) for x, s, p, c, ks in txs]
+        self.n_tx = len(txs)
+        col = lambda i, dt: np.asarray([t[i] for t in txs] or [0], dt)  # noqa: E731
+        self.txid, self.start_time, self.prepare_time = col(0, U64), col(1, U64), col(2, U64)
+        self.certify = col(3, np.uint8)
+        self.key_off, self.key, self.n_pairs = _pair_columns([t[4] for t in txs])
+
+    @classmethod
+    def from_columns(cls, txid, start_time, prepare_time, certify, key_off, key) -> "Prepares":
+        """A batch over columns already in the ABI's layout (key_off [n_tx+1], key [n_pairs])."""
+        b = cls.__new__(cls)
+        c = lambda a, dt: np.ascontiguousarray(a if len(a) else [0], dt)  # noqa: E731
+        b.n_tx = len(txid)
+        b.txid, b.start_time, b.prepare_time, b.certify = c(txid, U64), c(start_time, U64), c(prepare_time, U64), c(certify, np.uint8)
+        b.key_off = np.ascontiguousarray(key_off, U64)
+        b.n_pairs = len(key)
+        b.key = c(key, U64)
+        if len(b.key_off) != b.n_tx + 1:
+            raise ValueError("key_off must hold n_tx + 1 offsets")
+        return b
+
+    def transactions(self):
+        """The batch back as CertSim.prepare's tuples."""
+        o = self.key_off
+        return [(int(self.txid[t]), int(self.start_time[t]), int(self.prepare_time[t]), bool(self.certify[t]),
+                 [int(k) for k in self.key[int(o[t]):int(o[t + 1])]]) for t in range(self.n_tx)]
+
+    def as_struct(self) -> abi.am_prepares:
+        s = abi.am_prepares()
+        s.n_tx, s.n_pairs = self.n_tx, self.n_pairs
+        p = lambda a: a.ctypes.data  # noqa: E731
+        s.txid, s.start_time, s.prepare_time, s.certify = p(self.txid), p(self.start_time), p(self.prepare_time), p(self.certify)
+        s.key_off, s.key = p(self.key_off), p(self.key)
+        return s
+
+
+class Finishes:
+    """am_finishes in host memory: a batch of commit/5 and abort/2 clean-ups (clean_and_notify/3).
+    txs: [(txid, commit_time, committed, [key, ...])], the tuples CertSim.finish takes."""
+
+    def __init__(self, txs: Sequence[Tuple[int, int, bool, Sequence[int]]]):
+        txs = [(int(x), int(ct), bool(c), [int(k) for k in ks]) for x, ct, c, ks in txs]
+        self.n_tx = len(txs)
+        col = lambda i, dt: np.asarray([t[i] for t in txs] or [0], dt)  # noqa: E731
+        self.txid, self.commit_time, self.committed = col(0, U64), col(1, U64), col(2, np.uint8)
+        self.key_off, self.key, self.n_pairs = _pair_columns([t[3] for t in txs])
+
+    @classmethod
+    def from_columns(cls, txid, commit_time, committed, key_off, key) -> "Finishes":
+        """A batch over columns already in the ABI's layout (key_off [n_tx+1], key [n_pairs])."""
+        b = cls.__new__(cls)
+        c = lambda a, dt: np.ascontiguousarray(a if len(a) else [0], dt)  # noqa: E731
+        b.n_tx = len(txid)
+        b.txid, b.commit_time, b.committed = c(txid, U64), c(commit_time, U64), c(committed, np.uint8)
+        b.key_off = np.ascontiguousarray(key_off, U64)
+        b.n_pairs = len(key)
+        b.key = c(key, U64)
+        if len(b.key_off) != b.n_tx + 1:
+            raise ValueError("key_off must hold n_tx + 1 offsets")
+        return b
+
+    def transactions(self):
+        """The batch back as CertSim.finish's tuples."""
+        o = self.key_off
+        return [(int(self.txid[t]), int(self.commit_time[t]), bool(self.committed[t]),
+                 [int(k) for k in self.key[int(o[t]):int(o[t + 1])]]) for t in range(self.n_tx)]
+
+    def as_struct(self) -> abi.am_finishes:
+        s = abi.am_finishes()
+        s.n_tx, s.n_pairs = self.n_tx, self.n_pairs
+        p = lambda a: a.ctypes.data  # noqa: E731
+        s.txid, s.commit_time, s.committed = p(self.txid), p(self.commit_time), p(self.committed)
+        s.key_off, s.key = p(self.key_off), p(self.key)
+        return s

@@ -111,6 +111,8 @@ enum am_status {
                                        get_from_snapshot_log (the log, not the cache); a vnode
                                        with a log (am_vnode_create_logged) serves the read */
   AM_ERR_NO_PERMISSIONS = 6,        /* {error, no_permissions} (am_generate_downstream)     */
+  AM_ERR_WRITE_CONFLICT = 7,        /* {error, write_conflict} (am_cert_prepare)             */
+  AM_ERR_NO_UPDATES = 8,            /* {error, no_updates} (am_cert_prepare / am_cert_finish) */
   AM_ERR_INVALID = -1,
   AM_ERR_HIP = -2,
   AM_ERR_RCCL = -3,
@@ -903,6 +905,73 @@ int am_plog_read_host(am_ctx *ctx, am_plog *plog, const am_read_batch *host_batc
  * am_vnode_log: the vnode's log (borrowed; NULL for a plain vnode). */
 int am_vnode_create_logged(am_ctx *ctx, uint32_t n_dc, uint64_t n_keys, am_vnode **out);
 int am_vnode_log(am_vnode *v, am_plog **plog);
+
+/* ---- the partition's write-write certification (am_cert.hip) ----
+ * clocksi_vnode:prepare/6, certification_check/4, commit/5's committed_tx insert and clean_prepared/3
+ * (src/clocksi_vnode.erl:450-632) and the read servers' check_clock/4 + check_prepared_list/3
+ * (src/clocksi_readitem_server.erl:236-264), for batches: a call leaves the tables, and returns the
+ * statuses, that serving the batch's transactions one at a time in batch order gives.  Keys, TxIds and
+ * times are opaque u64, every value legal.  Two open-addressed tables in HBM, sized by am_cert_create /
+ * am_cert_reserve and by nothing else: committed (key -> commit time; cap_keys keys) and prepared (a
+ * multimap key -> (txid, prepare time); cap_entries live entries after any number of prepare / finish
+ * cycles -- removals leave tombstones, which a prepare compacts away before it runs when they crowd
+ * the table).  record_commits = 0: no commit time is recorded (the reference's txn_cert off).
+ * Per-transaction statuses: AM_OK, AM_ERR_WRITE_CONFLICT, AM_ERR_NO_UPDATES.
+ *   prepare   a certifying transaction conflicts when a key has committed[k] > start_time, holds a
+ *             prepared entry of any transaction, or is named by an earlier transaction of the batch
+ *             that ended AM_OK; no conflict and no keys: AM_ERR_NO_UPDATES; else one entry
+ *             (txid, prepare_time) per distinct key that has no entry of this TxId yet
+ *   finish    no keys: AM_ERR_NO_UPDATES; else committed[k] = commit_time for every key when committed
+ *             (the last transaction of the batch wins), and the entry (k, txid) leaves every key
+ * A malformed batch (key_off not non-decreasing from 0 to n_pairs; 2^32 or more pairs or transactions)
+ * returns AM_ERR_INVALID; a prepare whose AM_OK transactions need more than cap_entries live entries,
+ * or a finish that needs more than cap_keys committed keys, returns AM_ERR_CAPACITY; both leave the
+ * tables and dev_status untouched (the device decides before its first insert).  The structs live in
+ * host memory; the plain calls take device columns and leave their work on the context's stream, the
+ * _host twins take host columns and block. */
+#define AM_CERT_SPIN_WAIT_MS 10 /* ?SPIN_WAIT, include/antidote.hrl:53 */
+typedef struct am_cert am_cert;
+typedef struct am_prepares {
+  uint64_t n_tx, n_pairs;
+  const uint64_t *txid, *start_time, *prepare_time; /* [n_tx] */
+  const uint8_t *certify;                           /* [n_tx] */
+  const uint64_t *key_off;                          /* [n_tx+1] */
+  const uint64_t *key;                              /* [n_pairs] */
+} am_prepares;
+typedef struct am_finishes {
+  uint64_t n_tx, n_pairs;
+  const uint64_t *txid, *commit_time; /* [n_tx] */
+  const uint8_t *committed;           /* [n_tx] */
+  const uint64_t *key_off;            /* [n_tx+1] */
+  const uint64_t *key;                /* [n_pairs] */
+} am_finishes;
+int am_cert_create(am_ctx *ctx, uint64_t cap_keys, uint64_t cap_entries, int record_commits, am_cert **out);
+int am_cert_destroy(am_cert *cert);
+/* New capacities (the only call that allocates table memory): new buffers, a rehash kernel, a stream
+ * synchronize, then the old buffers are freed.  AM_ERR_INVALID below the live content.  Blocks. */
+int am_cert_reserve(am_cert *cert, uint64_t cap_keys, uint64_t cap_entries);
+int am_cert_prepare(am_cert *cert, const am_prepares *dev, int32_t *dev_status);
+int am_cert_prepare_host(am_cert *cert, const am_prepares *host, int32_t *host_status);
+int am_cert_finish(am_cert *cert, const am_finishes *dev, int32_t *dev_status);
+int am_cert_finish_host(am_cert *cert, const am_finishes *host, int32_t *host_status);
+/* wait_ms[i]: (start - now) div 1000 + 1 when start > now; else AM_CERT_SPIN_WAIT_MS when the key holds
+ * a prepared entry with time <= start; else 0 */
+int am_cert_read_ready(am_cert *cert, uint64_t n, const uint64_t *dev_key, const uint64_t *dev_start, uint64_t now,
+                       uint64_t *dev_wait_ms);
+int am_cert_read_ready_host(am_cert *cert, uint64_t n, const uint64_t *host_key, const uint64_t *host_start,
+                            uint64_t now, uint64_t *host_wait_ms);
+/* get_min_prep/1: the smallest prepare time in the table; *present = 0 when it is empty.  Blocks. */
+int am_cert_min_prepared(am_cert *cert, uint64_t *time, int *present);
+/* Test accessor: the key's commit time (0 = none) and its prepared entries sorted by (time, txid) to
+ * the host arrays txid / time [cap]; *n = their number (AM_ERR_CAPACITY when cap is smaller: the
+ * arrays are not written).  Blocks. */
+int am_cert_key_info(am_cert *cert, uint64_t key, uint64_t *commit_time, uint64_t cap, uint64_t *txid, uint64_t *time,
+                     uint64_t *n);
+int am_cert_size(am_cert *cert, uint64_t *committed_keys, uint64_t *prepared_entries, uint64_t *cap_keys,
+                 uint64_t *cap_entries);
+/* counters since create (NULL outputs are skipped): resolve rounds launched, status-block readbacks,
+ * compactions of the prepared table */
+int am_cert_stats(am_cert *cert, uint64_t *rounds, uint64_t *readbacks, uint64_t *compactions);
 
 /* ---- op-cache ingestion + garbage collection ----
  * Builds a new store from `st` (st is unchanged; destroy it when no read uses it):
