@@ -37,6 +37,7 @@ AM_ERR_NO_PERMISSIONS = 6  # {error, no_permissions} (am_generate_downstream)
 AM_ERR_WRITE_CONFLICT = 7  # {error, write_conflict} (am_cert_prepare)
 AM_ERR_NO_UPDATES = 8  # {error, no_updates} (am_cert_prepare / am_cert_finish)
 AM_CERT_SPIN_WAIT_MS = 10
+AM_DEP_BAD_PART, AM_DEP_BAD_DC, AM_DEP_BAD_TIME = 0x1, 0x2, 0x4  # am_dep_deliver's *bad
 AM_ERR_INVALID = -1
 AM_ERR_UNSUPPORTED = -5
 AM_FLAG_MISSING_DC_LOGGED = 0x1
@@ -148,6 +149,14 @@ class am_finishes(ctypes.Structure):
     _fields_ = [
         ("n_tx", c_uint64), ("n_pairs", c_uint64),
         ("txid", c_void_p), ("commit_time", c_void_p), ("committed", c_void_p), ("key_off", c_void_p), ("key", c_void_p),
+    ]
+
+
+class am_dep_txns(ctypes.Structure):
+    _fields_ = [
+        ("n_tx", c_uint64),
+        ("part", c_void_p), ("dc", c_void_p), ("timestamp", c_void_p), ("snap_vc", c_void_p), ("ping", c_void_p),
+        ("tag", c_void_p),
     ]
 
 
@@ -302,6 +311,21 @@ SIGNATURES = [
                                  POINTER(c_uint64)]),
     ("am_cert_size", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("am_cert_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("am_dep_create", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_uint64, c_void_p, POINTER(c_void_p)]),
+    ("am_dep_destroy", c_int, [c_void_p]),
+    ("am_dep_reserve", c_int, [c_void_p, c_uint64]),
+    ("am_dep_set_clock", c_int, [c_void_p, c_uint32, c_void_p, c_uint32]),
+    ("am_dep_set_drop_ping", c_int, [c_void_p, c_int]),
+    ("am_dep_clear", c_int, [c_void_p]),
+    ("am_dep_deliver", c_int, [c_void_p, POINTER(am_dep_txns), c_uint64, c_uint64, c_void_p, c_void_p, POINTER(c_uint64),
+                               POINTER(c_uint32)]),
+    ("am_dep_deliver_host", c_int, [c_void_p, POINTER(am_dep_txns), c_uint64, c_uint64, c_void_p, c_void_p,
+                                    POINTER(c_uint64), POINTER(c_uint32)]),
+    ("am_dep_clocks", c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p)]),
+    ("am_dep_clock_host", c_int, [c_void_p, c_uint32, c_void_p, POINTER(c_uint32)]),
+    ("am_dep_queue", c_int, [c_void_p, c_uint32, c_uint32, c_uint64, c_void_p, POINTER(c_uint64)]),
+    ("am_dep_size", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("am_dep_stats", c_int, [c_void_p, POINTER(c_uint64)]),
     ("am_codec_create", c_int, [POINTER(c_void_p)]),
     ("am_codec_destroy", c_int, [c_void_p]),
     ("am_codec_intern", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),

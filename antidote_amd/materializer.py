@@ -21,7 +21,7 @@ import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from . import abi
-from .oplog import Commits, Effects, Finishes, HostBatch, HostLog, Op, Prepares, Read, Updates, WriteSet
+from .oplog import Commits, DepTxns, Effects, Finishes, HostBatch, HostLog, Op, Prepares, Read, Updates, WriteSet
 
 IGNORE = None
 
@@ -630,6 +630,122 @@ class Certifier:
             self.handle = ctypes.c_void_p()
 
 
+class DepBuffer:
+    """The dependency buffers of every partition a GPU owns, in HBM (am_dep): inter_dc_dep_vnode's
+    queues, try_store/2 and partition clock (src/inter_dc_dep_vnode.erl:94-154, 187-238), for batches
+    of arrivals.  tests/depsim.py restates the reference; deliver() returns, per partition, what
+    serving the batch one arrival at a time through it returns.  A call that fails raises abi.AmError
+    with the code in .rc and the validity bits in .bad, and leaves queues and clocks as they were."""
+
+    def __init__(self, mat: "Materializer", n_dc: int, own_dc: int, n_part: int, cap_queued: int, order=None):
+        import numpy as np
+        self.mat, self.handle = mat, ctypes.c_void_p()
+        self.n_dc, self.own_dc, self.n_part = n_dc, own_dc, n_part
+        o = np.ascontiguousarray(order, np.uint8) if order is not None else None
+        if o is not None and len(o) != n_dc:
+            raise ValueError("order must name every DC once")
+        self._check(mat.L.am_dep_create(mat.ctx, n_dc, own_dc, n_part, cap_queued, o.ctypes.data if o is not None else None,
+                                        ctypes.byref(self.handle)), "am_dep_create")
+
+    @staticmethod
+    def _check(rc: int, what: str, bad: int = 0):
+        if rc != 0:
+            msg = abi.lib().am_last_error()
+            e = abi.AmError(f"{what} failed rc={rc}: {msg.decode() if msg else ''}")
+            e.rc, e.bad = rc, bad
+            raise e
+
+    def deliver(self, txs, now: int) -> List[List[int]]:
+        """[(part, dc, timestamp, snapshot, ping, tag)] (or a DepTxns) -> per partition the tags of the
+        transactions delivered by this call, in delivery order."""
+        import numpy as np
+        b = txs if isinstance(txs, DepTxns) else DepTxns(self.n_dc, txs)
+        queued, _ = self.size()
+        cap_out = queued + b.n_tx
+        off, tag = np.zeros(self.n_part + 1, np.uint64), np.zeros(max(cap_out, 1), np.uint64)
+        s, n, bad = b.as_struct(), ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self.mat.L.am_dep_deliver_host(self.handle, ctypes.byref(s), int(now), cap_out, off.ctypes.data, tag.ctypes.data,
+                                            ctypes.byref(n), ctypes.byref(bad))
+        self._check(rc, "am_dep_deliver_host", int(bad.value))
+        return [[int(x) for x in tag[int(off[p]):int(off[p + 1])]] for p in range(self.n_part)]
+
+    def set_clock(self, part: int, vc: Dict[int, int]):
+        """set_dependency_clock: the partition's clock becomes vc."""
+        import numpy as np
+        row, pres = np.zeros(self.n_dc, np.uint64), 0
+        for d, v in vc.items():
+            row[d], pres = v, pres | (1 << d)
+        self._check(self.mat.L.am_dep_set_clock(self.handle, part, row.ctypes.data, pres), "am_dep_set_clock")
+
+    def set_drop_ping(self, on: bool):
+        self._check(self.mat.L.am_dep_set_drop_ping(self.handle, 1 if on else 0), "am_dep_set_drop_ping")
+
+    def clear(self):
+        """Every queue emptied and every clock new, as after the vnodes' init/1."""
+        self._check(self.mat.L.am_dep_clear(self.handle), "am_dep_clear")
+
+    def clock(self, part: int) -> Dict[int, int]:
+        import numpy as np
+        row, pres = np.zeros(self.n_dc, np.uint64), ctypes.c_uint32()
+        self._check(self.mat.L.am_dep_clock_host(self.handle, part, row.ctypes.data, ctypes.byref(pres)), "am_dep_clock_host")
+        return {d: int(row[d]) for d in range(self.n_dc) if (pres.value >> d) & 1}
+
+    def queue(self, part: int, dc: int) -> List[int]:
+        """The queued tags of one (partition, DC), oldest first."""
+        import numpy as np
+        cap = 64
+        while True:
+            n, tag = ctypes.c_uint64(), np.zeros(cap, np.uint64)
+            rc = self.mat.L.am_dep_queue(self.handle, part, dc, cap, tag.ctypes.data, ctypes.byref(n))
+            if rc == abi.AM_ERR_CAPACITY and n.value > cap:
+                cap = int(n.value)
+                continue
+            self._check(rc, "am_dep_queue")
+            return [int(x) for x in tag[:int(n.value)]]
+
+    def clocks(self) -> Tuple[int, int]:
+        """Device addresses of the clock matrix [n_part][n_dc] and the presence words [n_part]."""
+        vc, pres = ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self.mat.L.am_dep_clocks(self.handle, ctypes.byref(vc), ctypes.byref(pres)), "am_dep_clocks")
+        return int(vc.value), int(pres.value)
+
+    def gst_lanes(self) -> List[int]:
+        """am_gst_local_min over this buffer's clock matrix, read in place: the n_dc + 1 lanes the
+        node's GST merge starts from (absent DC = 2^64 - 1)."""
+        import numpy as np
+        vc, pres = self.clocks()
+        host = np.zeros(self.n_dc + 1, np.uint64)
+        lanes = self.mat.device_array(host)
+        try:
+            abi.check(self.mat.L.am_gst_local_min(self.mat.ctx, self.n_dc, self.n_part, vc, pres, None, lanes.ptr),
+                      "am_gst_local_min")
+            self.mat.sync()
+            lanes.download(host)
+            return [int(x) for x in host]
+        finally:
+            lanes.free()
+
+    def reserve(self, cap_queued: int):
+        self._check(self.mat.L.am_dep_reserve(self.handle, cap_queued), "am_dep_reserve")
+
+    def size(self) -> Tuple[int, int]:
+        """(queued entries, cap_queued)"""
+        v = [ctypes.c_uint64() for _ in range(2)]
+        self._check(self.mat.L.am_dep_size(self.handle, *[ctypes.byref(x) for x in v]), "am_dep_size")
+        return tuple(int(x.value) for x in v)
+
+    def readbacks(self) -> int:
+        v = ctypes.c_uint64()
+        self._check(self.mat.L.am_dep_stats(self.handle, ctypes.byref(v)), "am_dep_stats")
+        return int(v.value)
+
+    def close(self):
+        if self.handle:
+            if self.mat.ctx:
+                self.mat.L.am_dep_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+
 class Materializer:
     """A context on one GPU (device index = local rank)."""
 
@@ -691,6 +807,9 @@ class Materializer:
 
     def certifier(self, cap_keys: int, cap_entries: int, record_commits: bool = True) -> Certifier:
         return Certifier(self, cap_keys, cap_entries, record_commits)
+
+    def dep_buffer(self, n_dc: int, own_dc: int, n_part: int, cap_queued: int, order=None) -> DepBuffer:
+        return DepBuffer(self, n_dc, own_dc, n_part, cap_queued, order)
 
     def partition_log(self, n_dc: int, cap_tx: int = 1024, cap_eff: int = 4096, cap_var: int = 4096) -> PartitionLog:
         return PartitionLog(self, n_dc, cap_tx, cap_eff, cap_var)

@@ -755,6 +755,48 @@ class Prepares:
         return s
 
 
+class DepTxns:
+    """am_dep_txns in host memory: a batch of arrivals at the dependency buffer, in the order
+    inter_dc_dep_vnode:handle_transaction/1 receives them.  txs: [(part, dc, timestamp, snapshot, ping,
+    tag)], snapshot a dict DC -> time (a DC it lacks goes in as 0); times and tags are any u64."""
+
+    def __init__(self, n_dc: int, txs: Sequence[Tuple[int, int, int, Dict[int, int], bool, int]]):
+        self.n_dc, self.n_tx = n_dc, len(txs)
+        col = lambda i, dt: np.asarray([int(t[i]) for t in txs] or [0], dt)  # noqa: E731
+        self.part, self.dc, self.timestamp = col(0, np.uint32), col(1, np.uint8), col(2, U64)
+        self.ping, self.tag = col(4, np.uint8), col(5, U64)
+        self.snap_vc = np.zeros((max(self.n_tx, 1), n_dc), U64)
+        for i, t in enumerate(txs):
+            for d, v in t[3].items():
+                self.snap_vc[i, d] = v
+
+    @classmethod
+    def from_columns(cls, n_dc: int, part, dc, timestamp, snap_vc, ping, tag) -> "DepTxns":
+        """A batch over columns already in the ABI's layout (snap_vc [n_tx][n_dc])."""
+        b = cls.__new__(cls)
+        c = lambda a, dt: np.ascontiguousarray(a if len(a) else [0], dt)  # noqa: E731
+        b.n_dc, b.n_tx = n_dc, len(part)
+        b.part, b.dc, b.timestamp, b.ping, b.tag = c(part, np.uint32), c(dc, np.uint8), c(timestamp, U64), c(ping, np.uint8), c(tag, U64)
+        b.snap_vc = np.ascontiguousarray(snap_vc, U64).reshape(-1, n_dc) if b.n_tx else np.zeros((1, n_dc), U64)
+        if b.n_tx and b.snap_vc.shape[0] != b.n_tx:
+            raise ValueError("snap_vc must hold n_tx rows of n_dc entries")
+        return b
+
+    def transactions(self):
+        """The batch back as its tuples (a snapshot entry of 0 reads as absent)."""
+        return [(int(self.part[t]), int(self.dc[t]), int(self.timestamp[t]),
+                 {d: int(v) for d, v in enumerate(self.snap_vc[t]) if v}, bool(self.ping[t]), int(self.tag[t]))
+                for t in range(self.n_tx)]
+
+    def as_struct(self) -> abi.am_dep_txns:
+        s = abi.am_dep_txns()
+        s.n_tx = self.n_tx
+        p = lambda a: a.ctypes.data  # noqa: E731
+        s.part, s.dc, s.timestamp, s.snap_vc, s.ping, s.tag = (p(self.part), p(self.dc), p(self.timestamp), p(self.snap_vc),
+                                                               p(self.ping), p(self.tag))
+        return s
+
+
 class Finishes:
     """am_finishes in host memory: a batch of commit/5 and abort/2 clean-ups (clean_and_notify/3).
     txs: [(txid, commit_time, committed, [key, ...])], the tuples CertSim.finish takes."""

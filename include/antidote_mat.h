@@ -973,6 +973,76 @@ int am_cert_size(am_cert *cert, uint64_t *committed_keys, uint64_t *prepared_ent
  * compactions of the prepared table */
 int am_cert_stats(am_cert *cert, uint64_t *rounds, uint64_t *readbacks, uint64_t *compactions);
 
+/* ---- remote delivery: the dependency buffer of every partition a GPU owns (am_dep.hip) ----
+ * inter_dc_dep_vnode's queues, try_store/2 and partition clock (src/inter_dc_dep_vnode.erl:94-154,
+ * 187-238), for batches of arrivals: one FIFO per (partition, origin DC), every queued transaction gated
+ * on its partition's vectorclock.  A call leaves the queues and clocks, and returns the deliveries, that
+ * serving the batch one arrival at a time in batch order gives (tests/depsim.py restates the reference):
+ * an arrival is pushed to its queue, then rounds visit the DCs in `order`, storing each queue's heads
+ * while they pass (a ping always passes; a transaction passes when clock[own_dc := now][dc := 0] >=
+ * snapshot[dc := 0]; a pass sets clock[dc] = timestamp, a failing head sets clock[dc] = timestamp - 1,
+ * both sets, not maxima) until a round stores nothing.  Where the reference leaves a choice open:
+ * `order` is given at create (NULL = ascending) where the reference folds over dict:fetch_keys/1; one
+ * `now` (microseconds) holds for every arrival of a call; the clock matrix in HBM is always current
+ * where update_clock/3 publishes every 100 ms; a non-ping transaction with timestamp 0 is invalid
+ * (timestamp - 1 has no u64 form); n_tx == 0 changes nothing.
+ * The state lives in HBM and is sized by am_dep_create / am_dep_reserve only: cap_queued entries over
+ * all queues.  AM_ERR_INVALID (*bad says why: a partition or DC out of range, timestamp 0 on a
+ * transaction; also n_tx >= 2^32 or cap_out < queued + n_tx) and AM_ERR_CAPACITY (queued + n_tx >
+ * cap_queued, decided on the host before any kernel) leave queues, clocks and outputs untouched.
+ * The struct lives in host memory; am_dep_deliver takes device columns and outputs and leaves its work
+ * on the context's stream except for one readback of a status block (validity bits, *n_delivered, the
+ * new queued count); am_dep_deliver_host takes host columns and outputs and blocks.  Delivered non-ping
+ * transactions' tags come back partition-major: partition p's are out_tag[out_off[p] .. out_off[p+1]),
+ * in delivery order. */
+typedef struct am_dep am_dep;
+typedef struct am_dep_txns {          /* arrivals, in the order handle_transaction/1 receives them */
+  uint64_t n_tx;
+  const uint32_t *part;               /* [n_tx] partition index < n_part                         */
+  const uint8_t  *dc;                 /* [n_tx] origin DC index (#interdc_txn.dcid)              */
+  const uint64_t *timestamp;          /* [n_tx]                                                  */
+  const uint64_t *snap_vc;            /* [n_tx][n_dc] transaction-major, as am_commits.snap_vc;
+                                         a DC absent from the snapshot goes in as 0 (ge reads a
+                                         missing entry as 0: the two are the same to try_store)  */
+  const uint8_t  *ping;               /* [n_tx] or NULL = none: 1 = log_records == []            */
+  const uint64_t *tag;                /* [n_tx] the caller's handle, returned on delivery        */
+} am_dep_txns;
+#define AM_DEP_BAD_PART 0x1u
+#define AM_DEP_BAD_DC   0x2u
+#define AM_DEP_BAD_TIME 0x4u          /* timestamp 0 on a transaction that is not a ping */
+/* n_dc in 1..32, own_dc < n_dc, n_part >= 1, cap_queued in 1..2^30, order [n_dc] a permutation of the
+ * DC indices or NULL: anything else is AM_ERR_INVALID. */
+int am_dep_create(am_ctx *ctx, uint32_t n_dc, uint32_t own_dc, uint32_t n_part, uint64_t cap_queued,
+                  const uint8_t *order, am_dep **out);
+int am_dep_destroy(am_dep *dep);
+/* A new capacity (besides create the only call that allocates queue memory): new buffers are filled, the
+ * stream is synchronized, then the old buffers are freed.  AM_ERR_INVALID below the queued count.
+ * Blocks.  The clock matrix does not move. */
+int am_dep_reserve(am_dep *dep, uint64_t cap_queued);
+/* set_dependency_clock: partition part's clock becomes host_vc [n_dc] with the presence bits pres.  Blocks. */
+int am_dep_set_clock(am_dep *dep, uint32_t part, const uint64_t *host_vc, uint32_t pres);
+int am_dep_set_drop_ping(am_dep *dep, int on);
+/* A vnode restart (init/1, :88-90): every queue emptied, every clock new; drop_ping and the capacity stay.
+ * Frees nothing.  Blocks. */
+int am_dep_clear(am_dep *dep);
+/* dev_out_off [n_part + 1], dev_out_tag [cap_out], cap_out >= queued + n_tx; bad may be NULL. */
+int am_dep_deliver(am_dep *dep, const am_dep_txns *dev, uint64_t now, uint64_t cap_out, uint64_t *dev_out_off,
+                   uint64_t *dev_out_tag, uint64_t *n_delivered, uint32_t *bad);
+int am_dep_deliver_host(am_dep *dep, const am_dep_txns *host, uint64_t now, uint64_t cap_out, uint64_t *host_out_off,
+                        uint64_t *host_out_tag, uint64_t *n_delivered, uint32_t *bad);
+/* Device pointers to the clock matrix [n_part][n_dc] and the presence words [n_part], the layout
+ * am_gst_local_min takes: borrowed, valid until destroy, not moved by reserve; an absent entry holds 0.
+ * Calls on the same context stream are ordered. */
+int am_dep_clocks(am_dep *dep, const uint64_t **part_vc, const uint32_t **part_pres);
+/* Test accessors, both block: one partition's clock to host memory; the queued tags of one (partition,
+ * DC), oldest first, to the host array tag [cap] (*n = their number; AM_ERR_CAPACITY when cap is
+ * smaller: the array is not written). */
+int am_dep_clock_host(am_dep *dep, uint32_t part, uint64_t *vc, uint32_t *pres);
+int am_dep_queue(am_dep *dep, uint32_t part, uint32_t dc, uint64_t cap, uint64_t *tag, uint64_t *n);
+int am_dep_size(am_dep *dep, uint64_t *queued, uint64_t *cap_queued);
+/* status-block readbacks of am_dep_deliver since create */
+int am_dep_stats(am_dep *dep, uint64_t *readbacks);
+
 /* ---- op-cache ingestion + garbage collection ----
  * Builds a new store from `st` (st is unchanged; destroy it when no read uses it):
  *   1. prune_ops/2 (src/materializer_vnode.erl:565-604): for keys with prune_mask[k] != 0
