@@ -38,6 +38,10 @@ AM_ERR_WRITE_CONFLICT = 7  # {error, write_conflict} (am_cert_prepare)
 AM_ERR_NO_UPDATES = 8  # {error, no_updates} (am_cert_prepare / am_cert_finish)
 AM_CERT_SPIN_WAIT_MS = 10
 AM_DEP_BAD_PART, AM_DEP_BAD_DC, AM_DEP_BAD_TIME = 0x1, 0x2, 0x4  # am_dep_deliver's *bad
+AM_SUB_TXN, AM_SUB_RESP_TXN, AM_SUB_RESP_END = 0, 1, 2  # am_sub_rows.kind
+AM_SUB_BAD_PART, AM_SUB_BAD_DC, AM_SUB_BAD_TIME, AM_SUB_BAD_KIND = 0x1, 0x2, 0x4, 0x8  # am_sub_process's *bad
+AM_SUB_NORMAL, AM_SUB_BUFFERING = 0, 1
+SUB_COUNTS = ("delivered", "gaps", "dropped", "unexpected", "queued")  # counts[5], in order (AM_SUB_N_*)
 AM_ERR_INVALID = -1
 AM_ERR_UNSUPPORTED = -5
 AM_FLAG_MISSING_DC_LOGGED = 0x1
@@ -158,6 +162,18 @@ class am_dep_txns(ctypes.Structure):
         ("part", c_void_p), ("dc", c_void_p), ("timestamp", c_void_p), ("snap_vc", c_void_p), ("ping", c_void_p),
         ("tag", c_void_p),
     ]
+
+
+class am_sub_rows(ctypes.Structure):
+    _fields_ = [
+        ("n_rows", c_uint64),
+        ("kind", c_void_p), ("part", c_void_p), ("dc", c_void_p), ("prev_opid", c_void_p), ("last_opid", c_void_p),
+        ("timestamp", c_void_p), ("snap_vc", c_void_p), ("ping", c_void_p), ("tag", c_void_p),
+    ]
+
+
+class am_sub_gaps(ctypes.Structure):
+    _fields_ = [("part", c_void_p), ("dc", c_void_p), ("from_", c_void_p), ("to", c_void_p)]
 
 
 class am_synth_params(ctypes.Structure):
@@ -326,6 +342,24 @@ SIGNATURES = [
     ("am_dep_queue", c_int, [c_void_p, c_uint32, c_uint32, c_uint64, c_void_p, POINTER(c_uint64)]),
     ("am_dep_size", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     ("am_dep_stats", c_int, [c_void_p, POINTER(c_uint64)]),
+    ("am_sub_create", c_int, [c_void_p, c_uint32, c_uint32, c_uint64, c_int, POINTER(c_void_p)]),
+    ("am_sub_destroy", c_int, [c_void_p]),
+    ("am_sub_reserve", c_int, [c_void_p, c_uint64]),
+    ("am_sub_clear", c_int, [c_void_p]),
+    ("am_sub_set_last", c_int, [c_void_p, c_uint32, c_uint32, c_uint64]),
+    ("am_sub_set_reachable", c_int, [c_void_p, c_uint32]),
+    ("am_sub_process", c_int, [c_void_p, POINTER(am_sub_rows), c_uint64, c_void_p, POINTER(am_dep_txns), c_uint64,
+                               POINTER(am_sub_gaps), c_void_p, POINTER(c_uint32)]),
+    ("am_sub_process_host", c_int, [c_void_p, POINTER(am_sub_rows), c_uint64, c_void_p, POINTER(am_dep_txns), c_uint64,
+                                    POINTER(am_sub_gaps), c_void_p, POINTER(c_uint32)]),
+    ("am_sub_deliver", c_int, [c_void_p, c_void_p, POINTER(am_sub_rows), c_uint64, c_uint64, c_void_p, c_void_p,
+                               POINTER(c_uint64), c_uint64, POINTER(am_sub_gaps), c_void_p, POINTER(c_uint32)]),
+    ("am_sub_deliver_host", c_int, [c_void_p, c_void_p, POINTER(am_sub_rows), c_uint64, c_uint64, c_void_p, c_void_p,
+                                    POINTER(c_uint64), c_uint64, POINTER(am_sub_gaps), c_void_p, POINTER(c_uint32)]),
+    ("am_sub_stream", c_int, [c_void_p, c_uint32, c_uint32, POINTER(c_uint64), POINTER(c_uint32), c_uint64, c_void_p,
+                              POINTER(c_uint64)]),
+    ("am_sub_size", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("am_sub_stats", c_int, [c_void_p, POINTER(c_uint64)]),
     ("am_codec_create", c_int, [POINTER(c_void_p)]),
     ("am_codec_destroy", c_int, [c_void_p]),
     ("am_codec_intern", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),

@@ -777,3 +777,10 @@ int am_dep_stats(am_dep *c, uint64_t *readbacks) {
 }
 
 }  // extern "C"
+
+// am_internal.h: for am_sub.hip's chained call
+int am_dep_shape(const am_dep *c, am_ctx **ctx, uint32_t *n_dc, uint32_t *n_part) {
+  if (!c || !ctx || !n_dc || !n_part) return AM_ERR_INVALID;
+  *ctx = c->ctx, *n_dc = c->n_dc, *n_part = c->n_part;
+  return AM_OK;
+}

@@ -126,6 +126,9 @@ int am_ctx_scratch(am_ctx *ctx, int slot, size_t bytes, void **out);
 // copy `n` u64 counters device -> host through the pinned buffer (synchronizes the stream)
 int am_ctx_fetch(am_ctx *ctx, const void *dev, uint32_t n_u64, uint64_t *host);
 
+// am_dep.hip, for am_sub.hip's chained call: the context and shape a dependency buffer was created with
+int am_dep_shape(const am_dep *dep, am_ctx **ctx, uint32_t *n_dc, uint32_t *n_part);
+
 // return an am_dev_alloc block to the context (kept for reuse, or freed past the cache cap)
 extern "C" void am_dev_release(am_ctx *ctx, void *p);
 

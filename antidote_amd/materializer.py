@@ -21,7 +21,7 @@ import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from . import abi
-from .oplog import Commits, DepTxns, Effects, Finishes, HostBatch, HostLog, Op, Prepares, Read, Updates, WriteSet
+from .oplog import Commits, DepTxns, Effects, Finishes, HostBatch, HostLog, Op, Prepares, Read, SubRows, Updates, WriteSet
 
 IGNORE = None
 
@@ -746,6 +746,124 @@ class DepBuffer:
             self.handle = ctypes.c_void_p()
 
 
+class SubBuffer:
+    """The subscriber buffers of every partition a GPU owns, in HBM (am_sub): one inter_dc_sub_buf state
+    machine per (partition, origin DC) stream (src/inter_dc_sub_buf.erl:57-162), for batches of rows.
+    tests/subsim.py restates the reference; process() returns what serving the batch one row at a time
+    through it returns.  A call that fails raises abi.AmError with the code in .rc and the validity bits
+    in .bad, and leaves streams and queues as they were."""
+
+    def __init__(self, mat: "Materializer", n_dc: int, n_part: int, cap_queued: int, logging_enabled: bool = True):
+        self.mat, self.handle = mat, ctypes.c_void_p()
+        self.n_dc, self.n_part = n_dc, n_part
+        self._check(mat.L.am_sub_create(mat.ctx, n_dc, n_part, cap_queued, 1 if logging_enabled else 0, ctypes.byref(self.handle)),
+                    "am_sub_create")
+
+    _check = staticmethod(DepBuffer._check)
+
+    @staticmethod
+    def _gaps(n: int):
+        import numpy as np
+        cols = (np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint64),
+                np.zeros(max(n, 1), np.uint64))
+        g = abi.am_sub_gaps()
+        g.part, g.dc, g.from_, g.to = (c.ctypes.data for c in cols)
+        return cols, g
+
+    def process(self, rows, columns: bool = False):
+        """[(kind, part, dc, prev_opid, last_opid, timestamp, snapshot, ping, tag)] (or a SubRows) ->
+        (per partition the delivered tags in delivery order, the gaps [(part, dc, from, to)] in
+        triggering-row order, the counters {delivered, gaps, dropped, unexpected, queued}).  With
+        columns=True the first element is instead the delivered transactions as a DepTxns, partition-major,
+        and a fourth element holds its offsets [n_part + 1]."""
+        import numpy as np
+        b = rows if isinstance(rows, SubRows) else SubRows(self.n_dc, rows)
+        queued, _ = self.size()
+        cap_out = queued + b.n_rows
+        m = max(cap_out, 1)
+        off = np.zeros(self.n_part + 1, np.uint64)
+        part, dc, ts = np.zeros(m, np.uint32), np.zeros(m, np.uint8), np.zeros(m, np.uint64)
+        snap, ping, tag = np.zeros((m, self.n_dc), np.uint64), np.zeros(m, np.uint8), np.zeros(m, np.uint64)
+        out = abi.am_dep_txns()
+        out.part, out.dc, out.timestamp, out.snap_vc, out.ping, out.tag = (a.ctypes.data for a in (part, dc, ts, snap, ping, tag))
+        gcols, g = self._gaps(b.n_rows)
+        s, cnt, bad = b.as_struct(), np.zeros(5, np.uint64), ctypes.c_uint32()
+        rc = self.mat.L.am_sub_process_host(self.handle, ctypes.byref(s), cap_out, off.ctypes.data, ctypes.byref(out), b.n_rows,
+                                            ctypes.byref(g), cnt.ctypes.data, ctypes.byref(bad))
+        self._check(rc, "am_sub_process_host", int(bad.value))
+        counters = dict(zip(abi.SUB_COUNTS, (int(x) for x in cnt)))
+        gaps = [(int(gcols[0][i]), int(gcols[1][i]), int(gcols[2][i]), int(gcols[3][i])) for i in range(counters["gaps"])]
+        nd = counters["delivered"]
+        if columns:
+            return DepTxns.from_columns(self.n_dc, part[:nd], dc[:nd], ts[:nd], snap[:nd], ping[:nd], tag[:nd]), gaps, counters, off
+        return [[int(x) for x in tag[int(off[p]):int(off[p + 1])]] for p in range(self.n_part)], gaps, counters
+
+    def deliver_into(self, dep: DepBuffer, rows, now: int):
+        """process(rows), then dep.deliver of what came out in order, without the columns leaving HBM
+        (am_sub_deliver) -> (per partition the tags am_dep delivered, the gaps, the counters)."""
+        import numpy as np
+        b = rows if isinstance(rows, SubRows) else SubRows(self.n_dc, rows)
+        cap_out = dep.size()[0] + self.size()[0] + b.n_rows
+        off, tag = np.zeros(self.n_part + 1, np.uint64), np.zeros(max(cap_out, 1), np.uint64)
+        gcols, g = self._gaps(b.n_rows)
+        s, cnt, bad, n = b.as_struct(), np.zeros(5, np.uint64), ctypes.c_uint32(), ctypes.c_uint64()
+        rc = self.mat.L.am_sub_deliver_host(self.handle, dep.handle, ctypes.byref(s), int(now), cap_out, off.ctypes.data,
+                                            tag.ctypes.data, ctypes.byref(n), b.n_rows, ctypes.byref(g), cnt.ctypes.data,
+                                            ctypes.byref(bad))
+        self._check(rc, "am_sub_deliver_host", int(bad.value))
+        counters = dict(zip(abi.SUB_COUNTS, (int(x) for x in cnt)))
+        gaps = [(int(gcols[0][i]), int(gcols[1][i]), int(gcols[2][i]), int(gcols[3][i])) for i in range(counters["gaps"])]
+        return [[int(x) for x in tag[int(off[p]):int(off[p + 1])]] for p in range(self.n_part)], gaps, counters
+
+    def set_last(self, part: int, dc: int, opid: int):
+        """last_observed_opid of one stream: what request_op_id/3 returned after a restart."""
+        self._check(self.mat.L.am_sub_set_last(self.handle, part, dc, int(opid)), "am_sub_set_last")
+
+    def set_reachable(self, dcs):
+        """The DCs whose log reader answers: an iterable of DC indices, or a bit mask."""
+        mask = dcs if isinstance(dcs, int) else sum(1 << d for d in set(dcs))
+        self._check(self.mat.L.am_sub_set_reachable(self.handle, mask & 0xFFFFFFFF), "am_sub_set_reachable")
+
+    def clear(self):
+        """Every queue emptied and every stream at last = 0 in normal mode."""
+        self._check(self.mat.L.am_sub_clear(self.handle), "am_sub_clear")
+
+    def stream(self, part: int, dc: int) -> Tuple[int, int, List[int]]:
+        """(last_observed_opid, mode, the queued tags oldest first) of one stream."""
+        import numpy as np
+        cap = 64
+        while True:
+            last, mode, n, tag = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint64(), np.zeros(cap, np.uint64)
+            rc = self.mat.L.am_sub_stream(self.handle, part, dc, ctypes.byref(last), ctypes.byref(mode), cap, tag.ctypes.data,
+                                          ctypes.byref(n))
+            if rc == abi.AM_ERR_CAPACITY and n.value > cap:
+                cap = int(n.value)
+                continue
+            self._check(rc, "am_sub_stream")
+            return int(last.value), int(mode.value), [int(x) for x in tag[:int(n.value)]]
+
+    def reserve(self, cap_queued: int):
+        self._check(self.mat.L.am_sub_reserve(self.handle, cap_queued), "am_sub_reserve")
+
+    def size(self) -> Tuple[int, int]:
+        """(queued entries, cap_queued)"""
+        v = [ctypes.c_uint64() for _ in range(2)]
+        self._check(self.mat.L.am_sub_size(self.handle, *[ctypes.byref(x) for x in v]), "am_sub_size")
+        return tuple(int(x.value) for x in v)
+
+    def stats(self) -> Dict[str, int]:
+        """Counters since create: status-block readbacks."""
+        v = ctypes.c_uint64()
+        self._check(self.mat.L.am_sub_stats(self.handle, ctypes.byref(v)), "am_sub_stats")
+        return {"readbacks": int(v.value)}
+
+    def close(self):
+        if self.handle:
+            if self.mat.ctx:
+                self.mat.L.am_sub_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+
 class Materializer:
     """A context on one GPU (device index = local rank)."""
 
@@ -810,6 +928,9 @@ class Materializer:
 
     def dep_buffer(self, n_dc: int, own_dc: int, n_part: int, cap_queued: int, order=None) -> DepBuffer:
         return DepBuffer(self, n_dc, own_dc, n_part, cap_queued, order)
+
+    def sub_buffer(self, n_dc: int, n_part: int, cap_queued: int, logging_enabled: bool = True) -> SubBuffer:
+        return SubBuffer(self, n_dc, n_part, cap_queued, logging_enabled)
 
     def partition_log(self, n_dc: int, cap_tx: int = 1024, cap_eff: int = 4096, cap_var: int = 4096) -> PartitionLog:
         return PartitionLog(self, n_dc, cap_tx, cap_eff, cap_var)

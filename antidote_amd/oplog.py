@@ -797,6 +797,51 @@ class DepTxns:
         return s
 
 
+class SubRows:
+    """am_sub_rows in host memory: a batch of rows at the subscriber buffer, in arrival order.  rows:
+    [(kind, part, dc, prev_opid, last_opid, timestamp, snapshot, ping, tag)], kind one of abi.AM_SUB_*,
+    snapshot a dict DC -> time (a DC it lacks goes in as 0); op ids, times and tags are any u64."""
+
+    def __init__(self, n_dc: int, rows: Sequence[Tuple[int, int, int, int, int, int, Dict[int, int], bool, int]]):
+        self.n_dc, self.n_rows = n_dc, len(rows)
+        col = lambda i, dt: np.asarray([int(t[i]) for t in rows] or [0], dt)  # noqa: E731
+        self.kind, self.part, self.dc = col(0, np.uint8), col(1, np.uint32), col(2, np.uint8)
+        self.prev_opid, self.last_opid, self.timestamp = col(3, U64), col(4, U64), col(5, U64)
+        self.ping, self.tag = col(7, np.uint8), col(8, U64)
+        self.snap_vc = np.zeros((max(self.n_rows, 1), n_dc), U64)
+        for i, t in enumerate(rows):
+            for d, v in t[6].items():
+                self.snap_vc[i, d] = v
+
+    @classmethod
+    def from_columns(cls, n_dc: int, kind, part, dc, prev_opid, last_opid, timestamp, snap_vc, ping, tag) -> "SubRows":
+        """A batch over columns already in the ABI's layout (snap_vc [n_rows][n_dc])."""
+        b = cls.__new__(cls)
+        c = lambda a, dt: np.ascontiguousarray(a if len(a) else [0], dt)  # noqa: E731
+        b.n_dc, b.n_rows = n_dc, len(kind)
+        b.kind, b.part, b.dc = c(kind, np.uint8), c(part, np.uint32), c(dc, np.uint8)
+        b.prev_opid, b.last_opid, b.timestamp = c(prev_opid, U64), c(last_opid, U64), c(timestamp, U64)
+        b.ping, b.tag = c(ping, np.uint8), c(tag, U64)
+        b.snap_vc = np.ascontiguousarray(snap_vc, U64).reshape(-1, n_dc) if b.n_rows else np.zeros((1, n_dc), U64)
+        if b.n_rows and b.snap_vc.shape[0] != b.n_rows:
+            raise ValueError("snap_vc must hold n_rows rows of n_dc entries")
+        return b
+
+    def rows(self):
+        """The batch back as its tuples (a snapshot entry of 0 reads as absent)."""
+        return [(int(self.kind[t]), int(self.part[t]), int(self.dc[t]), int(self.prev_opid[t]), int(self.last_opid[t]),
+                 int(self.timestamp[t]), {d: int(v) for d, v in enumerate(self.snap_vc[t]) if v}, bool(self.ping[t]),
+                 int(self.tag[t])) for t in range(self.n_rows)]
+
+    def as_struct(self) -> abi.am_sub_rows:
+        s = abi.am_sub_rows()
+        s.n_rows = self.n_rows
+        p = lambda a: a.ctypes.data  # noqa: E731
+        s.kind, s.part, s.dc, s.prev_opid, s.last_opid = p(self.kind), p(self.part), p(self.dc), p(self.prev_opid), p(self.last_opid)
+        s.timestamp, s.snap_vc, s.ping, s.tag = p(self.timestamp), p(self.snap_vc), p(self.ping), p(self.tag)
+        return s
+
+
 class Finishes:
     """am_finishes in host memory: a batch of commit/5 and abort/2 clean-ups (clean_and_notify/3).
     txs: [(txid, commit_time, committed, [key, ...])], the tuples CertSim.finish takes."""

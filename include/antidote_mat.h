@@ -1043,6 +1043,110 @@ int am_dep_size(am_dep *dep, uint64_t *queued, uint64_t *cap_queued);
 /* status-block readbacks of am_dep_deliver since create */
 int am_dep_stats(am_dep *dep, uint64_t *readbacks);
 
+/* ---- remote ordering: the subscriber buffer of every partition a GPU owns (am_sub.hip) ----
+ * One inter_dc_sub_buf state machine per (partition, origin DC) stream (src/inter_dc_sub_buf.erl:57-162,
+ * src/inter_dc_sub_vnode.erl:84-94), for batches of arrivals: what produces the order in which
+ * inter_dc_dep_vnode:handle_transaction/1 -- am_dep_deliver -- receives transactions.  A stream holds
+ * last_observed_opid, a mode (normal | buffering) and a FIFO.  A call leaves the streams, and returns the
+ * outputs, that serving the batch's rows one at a time in batch order gives (tests/subsim.py restates
+ * the reference):
+ *   AM_SUB_TXN       {txn, Txn}: pushed; in normal mode process_queue/1 then runs
+ *   AM_SUB_RESP_TXN  one transaction of a {log_reader_resp, Txns}: in buffering mode delivered at once,
+ *                    uncompared; in normal mode not delivered and counted as unexpected
+ *   AM_SUB_RESP_END  ends a response (an empty response is a lone RESP_END; the row's transaction
+ *                    columns are ignored): in buffering mode last := the queue head's prev_opid (unchanged
+ *                    when the queue is empty), then process_queue/1; in normal mode counted as unexpected
+ * process_queue/1 compares the head's prev_opid with last: equal delivers (last := last_opid; for a ping
+ * prev_opid, whatever the last_opid column holds), smaller drops a duplicate, greater emits the gap
+ * (part, dc, last + 1, prev_opid) and sets buffering -- or, when the DC is not in the reachable mask,
+ * stays normal with the head kept for the stream's next TXN row, or, with logging disabled, delivers.
+ * Where the reference leaves a choice open: a stream starts at last = 0 (am_sub_set_last loads what
+ * request_op_id/3 returned); query/3's outcome is the reachable mask (default: every DC);
+ * logging_enabled is read at create; a TXN / RESP_TXN row that is not a ping with timestamp 0 makes the
+ * batch invalid (am_dep could not take it); n_rows == 0 changes nothing.
+ * The state lives in HBM and is sized by am_sub_create / am_sub_reserve only.  AM_ERR_INVALID (*bad says
+ * why; also n_rows >= 2^31, cap_out < queued + n_rows, cap_gaps < n_rows) and AM_ERR_CAPACITY (queued +
+ * n_rows > cap_queued, decided on the host before any kernel) leave streams, queues and outputs
+ * untouched.  The structs live in host memory; the device calls take device columns and leave their
+ * work on the context's stream except for one readback of a status block (validity bits and the five
+ * counters); the _host calls take host columns and block. */
+typedef struct am_sub am_sub;
+typedef struct am_sub_rows {          /* rows in arrival order */
+  uint64_t n_rows;
+  const uint8_t  *kind;               /* [n] AM_SUB_TXN | AM_SUB_RESP_TXN | AM_SUB_RESP_END              */
+  const uint32_t *part;               /* [n] partition index < n_part                                   */
+  const uint8_t  *dc;                 /* [n] origin DC index < n_dc                                     */
+  const uint64_t *prev_opid;          /* [n] #interdc_txn.prev_log_opid#op_number.local                 */
+  const uint64_t *last_opid;          /* [n] inter_dc_txn:last_log_opid/1's local; ignored for a ping   */
+  const uint64_t *timestamp;          /* [n] carried for am_dep                                         */
+  const uint64_t *snap_vc;            /* [n][n_dc] as am_dep_txns.snap_vc                               */
+  const uint8_t  *ping;               /* [n] or NULL = none: 1 = log_records == []                      */
+  const uint64_t *tag;                /* [n] the caller's handle                                        */
+} am_sub_rows;
+typedef struct am_sub_gaps {          /* [cap_gaps] each: the ranges to ask the origin's log reader for */
+  uint32_t *part;
+  uint8_t  *dc;
+  uint64_t *from, *to;
+} am_sub_gaps;
+#define AM_SUB_TXN 0
+#define AM_SUB_RESP_TXN 1
+#define AM_SUB_RESP_END 2
+#define AM_SUB_BAD_PART 0x1u
+#define AM_SUB_BAD_DC   0x2u
+#define AM_SUB_BAD_TIME 0x4u          /* timestamp 0 on a TXN / RESP_TXN row that is not a ping */
+#define AM_SUB_BAD_KIND 0x8u
+#define AM_SUB_NORMAL 0
+#define AM_SUB_BUFFERING 1
+/* counts[5] of a call */
+#define AM_SUB_N_DELIVERED 0
+#define AM_SUB_N_GAPS 1
+#define AM_SUB_N_DROPPED 2
+#define AM_SUB_N_UNEXPECTED 3
+#define AM_SUB_N_QUEUED 4             /* the new total over all queues */
+/* n_dc in 1..32, n_part >= 1, cap_queued in 1..2^30: anything else is AM_ERR_INVALID. */
+int am_sub_create(am_ctx *ctx, uint32_t n_dc, uint32_t n_part, uint64_t cap_queued, int logging_enabled, am_sub **out);
+int am_sub_destroy(am_sub *sub);
+/* A new capacity (besides create the only call that allocates queue memory).  AM_ERR_INVALID below the
+ * queued count.  Blocks. */
+int am_sub_reserve(am_sub *sub, uint64_t cap_queued);
+/* A vnode restart: every queue emptied, every stream at last = 0 in normal mode; the reachable mask,
+ * logging_enabled and the capacity stay.  Frees nothing.  Blocks. */
+int am_sub_clear(am_sub *sub);
+/* last_observed_opid of one stream (what request_op_id/3 returned after a restart).  Blocks. */
+int am_sub_set_last(am_sub *sub, uint32_t part, uint32_t dc, uint64_t opid);
+/* bit d: query/3 to DC d answers ok */
+int am_sub_set_reachable(am_sub *sub, uint32_t dc_mask);
+/* Delivered transactions come back partition-major as the columns of am_dep_txns: partition p's are
+ * entries [out_off[p], out_off[p+1]), ordered by the row that triggered the delivery, then by queue
+ * order.  dev_out_off [n_part + 1]; dev_out: the caller's columns of cap_out >= queued + n_rows entries
+ * (n_tx is ignored, a NULL column is skipped); the gaps in triggering-row order, cap_gaps >= n_rows;
+ * counts [5] (host); bad may be NULL. */
+int am_sub_process(am_sub *sub, const am_sub_rows *dev, uint64_t cap_out, uint64_t *dev_out_off, const am_dep_txns *dev_out,
+                   uint64_t cap_gaps, const am_sub_gaps *dev_gaps, uint64_t *counts, uint32_t *bad);
+int am_sub_process_host(am_sub *sub, const am_sub_rows *host, uint64_t cap_out, uint64_t *host_out_off,
+                        const am_dep_txns *host_out, uint64_t cap_gaps, const am_sub_gaps *host_gaps, uint64_t *counts,
+                        uint32_t *bad);
+/* am_sub_process into library scratch, then am_dep_deliver on those device columns: the transactions
+ * never visit the host.  All or nothing: before any kernel, sub and dep must share the context, n_part
+ * and n_dc (AM_ERR_INVALID), dep.queued + sub.queued + n_rows must fit dep's cap_queued
+ * (AM_ERR_CAPACITY) and cap_out must reach that bound (AM_ERR_INVALID).  The outputs are
+ * am_dep_deliver's (dev_out_off [n_part + 1], dev_out_tag [cap_out], *n_delivered by am_dep) and this
+ * buffer's gaps and counts. */
+int am_sub_deliver(am_sub *sub, am_dep *dep, const am_sub_rows *dev, uint64_t now, uint64_t cap_out, uint64_t *dev_out_off,
+                   uint64_t *dev_out_tag, uint64_t *n_delivered, uint64_t cap_gaps, const am_sub_gaps *dev_gaps,
+                   uint64_t *counts, uint32_t *bad);
+int am_sub_deliver_host(am_sub *sub, am_dep *dep, const am_sub_rows *host, uint64_t now, uint64_t cap_out,
+                        uint64_t *host_out_off, uint64_t *host_out_tag, uint64_t *n_delivered, uint64_t cap_gaps,
+                        const am_sub_gaps *host_gaps, uint64_t *counts, uint32_t *bad);
+/* Test accessor: one stream's last_observed_opid, mode (AM_SUB_NORMAL | AM_SUB_BUFFERING) and queued
+ * tags, oldest first, to the host array tag [cap] (*n = their number; AM_ERR_CAPACITY when cap is
+ * smaller: the array is not written).  Blocks. */
+int am_sub_stream(am_sub *sub, uint32_t part, uint32_t dc, uint64_t *last, uint32_t *mode, uint64_t cap, uint64_t *tag,
+                  uint64_t *n);
+int am_sub_size(am_sub *sub, uint64_t *queued, uint64_t *cap_queued);
+/* status-block readbacks of am_sub_process / am_sub_deliver since create */
+int am_sub_stats(am_sub *sub, uint64_t *readbacks);
+
 /* ---- op-cache ingestion + garbage collection ----
  * Builds a new store from `st` (st is unchanged; destroy it when no read uses it):
  *   1. prune_ops/2 (src/materializer_vnode.erl:565-604): for keys with prune_mask[k] != 0
